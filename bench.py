@@ -18,13 +18,17 @@ Per-GPU work is fixed as N grows (weak scaling); `value` = N * 160000 * steps / 
 its rays (parallel.shard_range), reassembled by the same all-gather; `value` = 160000 * steps / time.
 Inputs resident in HBM when the timed region starts: packed weights, camera poses.
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline      the dominant kernel, timed live with HIP events on the launch stream: split path = the fine pass's kernel on the
-                frame's ray count (launched again after the timed region); fused path = the ray kernel around every timed step.
-                `whole_render` prices all launches of a frame together, as rounds 1-3 priced the fused kernel
-  cpu_baseline  the CPU oracle on the host cores (N = 1 only; bounded sample)
-  configs       N = 1 only: BASELINE configs 3 and 4 on this GPU -- the stylised ray path, the 2-D style pass,
-                and a whole 504x378 trex frame -- each with its own live-timed value
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the headline's steps and reports them; `whole_render`
+prices all launches of a frame together (HIP events around every timed step), as rounds 1-3 priced the fused kernel.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0: `rgb`, `t`, and for N > 1 the gathered `frame`) as
+DIR/<name>.npy in float32.  `--full` adds the measurements that take runs of their own:
+  roofline        the dominant kernel, timed live with HIP events on the launch stream: split path = the fine pass's kernel on
+                  the frame's ray count (launched again after the timed region); fused path = the ray kernel around every timed
+                  step (a plain run of the fused path reports it too: it costs no extra launch)
+  alt_precisions  the headline again in the precisions of --alt-precision
+  cpu_baseline    the CPU oracle on the host cores (N = 1 only; bounded sample)
+  configs         N = 1 only: BASELINE configs 3 and 4 on this GPU -- the stylised ray path, the 2-D style pass,
+                  and a whole 504x378 trex frame -- each with its own live-timed value
 """
 import argparse
 import json
@@ -185,6 +189,22 @@ def time_loop(fn, steps, warmup):
         out = timed.run(i, lambda: fn(warmup + i))
     torch.cuda.synchronize()
     return time.perf_counter() - t0, timed.mean_ms(), out
+
+
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs at most
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy in float32.  Beyond DUMP_LIMIT in all, every array keeps the same fixed, seeded
+    sample of its rows (rows in their original order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = len(a) * DUMP_LIMIT // total
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def bench_style2d(precision, steps, warmup):
@@ -379,8 +399,9 @@ def bench_frame(precision, h, w, steps, warmup, styled=False):
             "rays_per_step": n, "kernel_ms": ms, "roofline": roof}
 
 
-def run_headline(args, precision, rank, world, dist):
-    """The timed headline run; returns the JSON dict on rank 0, None elsewhere."""
+def run_headline(args, precision, rank, world, dist, dump=None):
+    """The timed headline run; returns the JSON dict on rank 0, None elsewhere.  dump: directory for the outputs of the last
+    timed step (rank 0)."""
     from tgtc_style_amd import parallel, synth, utils
     renderer = make_renderer(precision, False)
     split = renderer.fused is True and renderer._split_is_faster()     # the library's choice for fp16x3 + fp16mx (include/tgtc_hip.h)
@@ -393,6 +414,7 @@ def run_headline(args, precision, rank, world, dist):
     timed = Timed(args.steps)
     # N > 1: the gather of frame i runs on a side stream while frame i+1 renders; two image buffers
     gather = None
+    last = {}               # what the last timed step's render returned
     if world > 1:
         gather = parallel.AsyncGather((lambda x: parallel.gather_rows(x, n_rays, rank, world, dist)) if by_rays
                                       else (lambda x: parallel.gather_frames(x, world, dist)))
@@ -403,6 +425,7 @@ def run_headline(args, precision, rank, world, dist):
         o, d = utils.gen_rays(H, W, focal, pose, first_pixel=lo, n=hi - lo)
         render = lambda: renderer.render(o, d, N_COARSE, N_FINE, near=0., far=1.)
         out = timed.run(timed_idx, render) if timed_idx is not None else render()
+        last.update(out)
         image = images[i % 2]
         if gather is not None:
             gather.reusable(i)
@@ -436,6 +459,8 @@ def run_headline(args, precision, rank, world, dist):
     assert bool(torch.isfinite(frame).all())
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, dict(last, frame=frame) if world > 1 else last)
 
     render_ms = timed.mean_ms()
     rays_total = (1 if by_rays else world) * n_rays * args.steps
@@ -445,7 +470,8 @@ def run_headline(args, precision, rank, world, dist):
              "mfma_products_per_algorithmic_product": mfma_per_product(precision)}
     whole["frac"] = whole["achieved"] / PEAK_FP16_TFLOPS
     whole["mfma_pipe_frac"] = whole["frac"] * whole["mfma_products_per_algorithmic_product"]
-    if split:
+    priced = args.full or not split     # the split path's kernels are timed on launches of their own: --full only
+    if split and priced:
         # the dominant kernel of the split path: the fine pass (192 depths per ray, full network) on the two-tile per-sample
         # kernel -- ONE launch per frame, timed live here on the launch stream with the frame's ray count
         from tgtc_style_amd import hip
@@ -477,7 +503,7 @@ def run_headline(args, precision, rank, world, dist):
         traffic, provenance = pmc_traffic("nerf_mx2_kernel")
         algo_bytes = rays_launch * (2 * 3 * 8 + n_all * 4 + n_all * 16)      # rays + depths in, rgb + sigma per sample out
         prod = MFMA_PER_PRODUCT["fp16mx"]
-    else:
+    elif not split:
         kernel_ms = render_ms
         flop_launch = float(FLOP_PER_RAY) * rays_launch
         kname = ("%s (whole render of %d rays in one launch: PE + coarse MLP x128, fine sampling, PE + fine MLP x192, compositing)"
@@ -485,11 +511,7 @@ def run_headline(args, precision, rank, world, dist):
         traffic, provenance = pmc_traffic("fused_render_kernel:%s" % precision) if fused else (None, "chain: not profiled")
         algo_bytes = rays_launch * BYTES_PER_RAY
         prod = mfma_per_product(precision)
-    achieved = flop_launch / (kernel_ms * 1e-3) / 1e12
-    if traffic and rays_launch != n_rays:   # the PMC pass profiled whole-frame launches; a ray range streams in proportion
-        traffic *= rays_launch / n_rays
-        provenance += "; scaled by %d / %d rays of this launch" % (rays_launch, n_rays)
-    return {
+    line = {
         "metric": "rays/sec (128c+64f samples) on fern 400x400",
         "value": rays_total / dt,
         "unit": "rays/s",
@@ -508,19 +530,58 @@ def run_headline(args, precision, rank, world, dist):
                    "rays_per_step": (1 if by_rays else world) * n_rays, "precision": precision,
                    "sharding": "rays" if by_rays else "frames", "algorithmic_mflop_per_ray": FLOP_PER_RAY / 1e6,
                    "precision_note": NOTES.get(precision, "")},
-        "roofline": {"bound": "mfma", "kernel": kname,
-                     "achieved": achieved, "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP16_TFLOPS,
-                     "traffic": traffic, "traffic_source": provenance,
-                     "algorithmic_bytes_per_launch": algo_bytes,
-                     "traffic_over_algorithmic": (traffic / algo_bytes) if traffic else None,
-                     "kernel_ms": kernel_ms, "algorithmic_tflop_per_launch": flop_launch / 1e12,
-                     "mfma_products_per_algorithmic_product": prod,
-                     "mfma_pipe_frac": achieved * prod / PEAK_FP16_TFLOPS},
         # every launch of one frame's render together (what `value` is made of), priced like rounds 1-3 priced the fused kernel
         "whole_render": whole,
         "render_path": "split (per-sample kernels; fine pass on the two-tile kernel)" if split else ("fused ray kernel" if fused else "per-sample kernel chain"),
         "whole_path_tflops": rays_total / dt * FLOP_PER_RAY / 1e12,
     }
+    if not priced:
+        return line
+    achieved = flop_launch / (kernel_ms * 1e-3) / 1e12
+    if traffic and rays_launch != n_rays:   # the PMC pass profiled whole-frame launches; a ray range streams in proportion
+        traffic *= rays_launch / n_rays
+        provenance += "; scaled by %d / %d rays of this launch" % (rays_launch, n_rays)
+    line["roofline"] = {"bound": "mfma", "kernel": kname,
+                        "achieved": achieved, "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP16_TFLOPS,
+                        "traffic": traffic, "traffic_source": provenance,
+                        "algorithmic_bytes_per_launch": algo_bytes,
+                        "traffic_over_algorithmic": (traffic / algo_bytes) if traffic else None,
+                        "kernel_ms": kernel_ms, "algorithmic_tflop_per_launch": flop_launch / 1e12,
+                        "mfma_products_per_algorithmic_product": prod,
+                        "mfma_pipe_frac": achieved * prod / PEAK_FP16_TFLOPS}
+    return line
+
+
+def run_full(args, line, rank, world, dist):
+    """--full: the measurements beyond the headline, added to rank 0's `line`."""
+    alts = [p for p in args.alt_precision.split(",") if p and p != args.precision]
+    alt_lines = [run_headline(args, p, rank, world, dist) for p in alts]   # every rank joins the collectives
+    if rank != 0:
+        return
+    for p, alt in zip(alts, alt_lines):
+        entry = {k: alt[k] for k in ("value", "ms_per_step", "dtype")}
+        entry.update(precision=p, roofline_frac=alt["roofline"]["frac"], kernel_ms=alt["roofline"]["kernel_ms"],
+                     mfma_pipe_frac=alt["roofline"]["mfma_pipe_frac"], note=NOTES.get(p, ""))
+        line.setdefault("alt_precisions", []).append(entry)
+    if world > 1:
+        return
+    short = int(os.environ.get("TGTC_BENCH_CONFIG_STEPS", max(2, min(args.steps, 3))))   # (profiling runs vary it)
+    cfg = {}
+    wanted = [c for c in args.configs.split(",") if c]
+    if "styled" in wanted:      # BASELINE config 3, ray path: the stylised chain (NeRF + concat MLP + style MLP)
+        cfg["styled"] = dict(bench_frame("fp16x3", H, W, short, 1, styled=True),
+                             metric="rays/sec (128c+64f) on fern 400x400, stylised (concat + style MLPs)")
+    if "style2d" in wanted:     # BASELINE config 3, per-frame ViT + CNN decoder + VGG pass
+        cfg["style2d"] = bench_style2d("fp16x3", short, 1)
+    if "trex_rays" in wanted:   # BASELINE config 4's frame on one GPU (its 8 ray ranges are this frame's slices)
+        cfg["trex_rays"] = dict(bench_frame(args.precision, 378, 504, short, 1),
+                                metric="rays/sec (128c+64f) on a whole trex 504x378 frame (190512 rays), one GPU")
+    if "train_step" in wanted:  # SURVEY 8f rank 4 (training side)
+        cfg["train_step"] = bench_train_step(6, 3)
+    if cfg:
+        line["configs"] = cfg
+    if args.cpu_rays > 0:
+        line["cpu_baseline"] = cpu_baseline(args.cpu_rays)
 
 
 def main():
@@ -533,11 +594,15 @@ def main():
     ap.add_argument("--sharding", default="frames", choices=["frames", "rays"],
                     help="N > 1: frames = every rank a whole frame per step (weak scaling, BASELINE config 5 style); "
                          "rays = one frame per step, contiguous ray ranges per rank (BASELINE config 4, strong scaling)")
-    ap.add_argument("--cpu-rays", type=int, default=8192, help="rays of the CPU baseline sample (0 disables)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the split path's per-kernel roofline, --alt-precision, --configs and the CPU baseline")
+    ap.add_argument("--cpu-rays", type=int, default=8192, help="--full: rays of the CPU baseline sample (0 disables)")
     ap.add_argument("--alt-precision", default="fp16x3,fp16",
-                    help="further precisions (comma separated) reported under `alt_precisions` ('' disables)")
+                    help="--full: further precisions (comma separated) reported under `alt_precisions` ('' disables)")
     ap.add_argument("--configs", default="styled,style2d,trex_rays,train_step",
-                    help="N = 1: further BASELINE configs measured after the headline and reported under `configs` ('' disables)")
+                    help="--full, N = 1: further BASELINE configs measured after the headline and reported under `configs` ('' disables)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -557,33 +622,10 @@ def main():
             dist.init_process_group(backend)
     torch.cuda.set_device(local)
 
-    line = run_headline(args, args.precision, rank, world, dist)
-    alts = [p for p in args.alt_precision.split(",") if p and p != args.precision]
-    alt_lines = [run_headline(args, p, rank, world, dist) for p in alts]   # every rank joins the collectives
+    line = run_headline(args, args.precision, rank, world, dist, dump=args.dump_outputs)
+    if args.full:
+        run_full(args, line, rank, world, dist)
     if rank == 0:
-        for p, alt in zip(alts, alt_lines):
-            entry = {k: alt[k] for k in ("value", "ms_per_step", "dtype")}
-            entry.update(precision=p, roofline_frac=alt["roofline"]["frac"], kernel_ms=alt["roofline"]["kernel_ms"],
-                         mfma_pipe_frac=alt["roofline"]["mfma_pipe_frac"], note=NOTES.get(p, ""))
-            line.setdefault("alt_precisions", []).append(entry)
-        if world == 1:
-            short = int(os.environ.get("TGTC_BENCH_CONFIG_STEPS", max(2, min(args.steps, 3))))   # (profiling runs vary it)
-            cfg = {}
-            wanted = [c for c in args.configs.split(",") if c]
-            if "styled" in wanted:      # BASELINE config 3, ray path: the stylised chain (NeRF + concat MLP + style MLP)
-                cfg["styled"] = dict(bench_frame("fp16x3", H, W, short, 1, styled=True),
-                                     metric="rays/sec (128c+64f) on fern 400x400, stylised (concat + style MLPs)")
-            if "style2d" in wanted:     # BASELINE config 3, per-frame ViT + CNN decoder + VGG pass
-                cfg["style2d"] = bench_style2d("fp16x3", short, 1)
-            if "trex_rays" in wanted:   # BASELINE config 4's frame on one GPU (its 8 ray ranges are this frame's slices)
-                cfg["trex_rays"] = dict(bench_frame(args.precision, 378, 504, short, 1),
-                                        metric="rays/sec (128c+64f) on a whole trex 504x378 frame (190512 rays), one GPU")
-            if "train_step" in wanted:  # SURVEY 8f rank 4 (training side)
-                cfg["train_step"] = bench_train_step(6, 3)
-            if cfg:
-                line["configs"] = cfg
-            if args.cpu_rays > 0:
-                line["cpu_baseline"] = cpu_baseline(args.cpu_rays)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

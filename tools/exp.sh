@@ -6,7 +6,7 @@
 # Every round runs the timer once per build (TGTC_LIB=csrc/libtgtc_dev_<tag>.so; `product` = the shipped library); -t first
 # runs the named GPU tests against every build.  Default timer: tools/time_fused.py fp16x3+fp16mx (fused ray kernel and the
 # per-sample chain, whole 400x400 frame).  Other timers: "python tools/time_styled.py fp16x3", "python tools/time_train.py",
-# "python bench.py --steps 6 --warmup 2 --cpu-rays 0 --alt-precision '' --configs style2d".
+# "python bench.py --full --steps 6 --warmup 2 --cpu-rays 0 --alt-precision '' --configs style2d".
 # This script replaces the one-off tools/exp1.sh ... exp21.sh of rounds 1-2 (git history has them; their results are
 # profiles/r1_kernel_variants.md and profiles/r2_kernel_variants.md).
 N=3; TESTS=""; CMD="python tools/time_fused.py fp16x3+fp16mx"

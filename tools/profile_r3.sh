@@ -20,7 +20,7 @@ run() {   # run <tag> <bench args...>
   echo "$OUT exit $?"
   python3 tools/pmc_summary.py $OUT > $OUT/summary.txt 2>&1
 }
-COMMON="--steps 4 --warmup 2 --cpu-rays 0 --alt-precision="
+COMMON="--full --steps 4 --warmup 2 --cpu-rays 0 --alt-precision="
 run headline_x3mx $COMMON --configs= --precision fp16x3+fp16mx && \
 run headline_x3   $COMMON --configs= --precision fp16x3 && \
 run styled        $COMMON --configs=styled --precision fp16x3+fp16mx

@@ -1,12 +1,12 @@
 #!/bin/bash
-# Per-kernel times of ONE steady-state frame of the 2-D style pass (bench.py --configs style2d only).  Two profiled runs with
+# Per-kernel times of ONE steady-state frame of the 2-D style pass (bench.py --full --configs style2d only).  Two profiled runs with
 # different step counts; their difference, divided by the extra frames, is what a frame costs -- handle creation (one
 # host-to-device upload per weight tensor: ~300 `__amd_rocclr_copyBuffer` blits) and warm-up drop out.  (Round 2's table
 # divided the whole process by the frame count, set-up copies included, which VERDICT r3 read as 312 copies per frame.)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_s2d; rm -rf $OUT; mkdir -p $OUT; cd $R
 for S in 4 12; do
-  TGTC_BENCH_CONFIG_STEPS=$S rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$S -- python3 bench.py --steps 2 --warmup 2 --cpu-rays 0 --alt-precision "" --configs style2d > $OUT/bench_$S.json 2> $OUT/err_$S.txt
+  TGTC_BENCH_CONFIG_STEPS=$S rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$S -- python3 bench.py --full --steps 2 --warmup 2 --cpu-rays 0 --alt-precision "" --configs style2d > $OUT/bench_$S.json 2> $OUT/err_$S.txt
 done
 python3 - <<'PY'
 import csv, glob, os

@@ -22,7 +22,7 @@ def mean(run, sub, counter, key):
 
 head = subprocess.check_output(['git', 'rev-parse', '--short', 'HEAD']).decode().strip()
 d = {"collected": "tools/profile_%s.sh on MI355X" % tag + ": rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes of "
-                  "`python3 bench.py --steps 4 --warmup 2 --cpu-rays 0 --alt-precision= --configs=<one> --precision <p>`; means per dispatch; "
+                  "`python3 bench.py --full --steps 4 --warmup 2 --cpu-rays 0 --alt-precision= --configs=<one> --precision <p>`; means per dispatch; "
                   "summaries profiles/%s_<run>_rocprof_summary.txt" % tag,
      "commit": head,
      "note": "FETCH_SIZE / WRITE_SIZE are in KB and count L2<->fabric requests (Infinity-Cache hits included).  fetch_bytes = 2 x "

@@ -12,10 +12,10 @@ tests)
   python -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1; echo "pytest rc $?" | tee -a $O/status.txt; tail -3 $O/pytest_gpu.txt;;
 bench)
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc $?" | tee -a $O/status.txt; tail -2 $O/smoke.txt
-  python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/status.txt; tail -c 600 $O/bench_default.json
+  python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/status.txt; tail -c 600 $O/bench_default.json
   for sh in frames rays; do
     TGTC_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-        bench.py --gpus 2 --steps 3 --warmup 1 --sharding $sh --cpu-rays 0 --alt-precision "" --configs "" > $O/bench_2rank_$sh.json 2> $O/bench_2rank_$sh.err
+        bench.py --full --gpus 2 --steps 3 --warmup 1 --sharding $sh --cpu-rays 0 --alt-precision "" --configs "" > $O/bench_2rank_$sh.json 2> $O/bench_2rank_$sh.err
     echo "2-rank $sh rc $?" | tee -a $O/status.txt; tail -c 400 $O/bench_2rank_$sh.json; echo
   done;;
 profile)
