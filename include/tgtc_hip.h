@@ -116,34 +116,39 @@ int tgtc_composite_backward(const float* rgb, const float* sigma, const float* t
 int tgtc_sample_fine(const double* rays_o, const double* rays_d, const float* ts, const float* weights,
                      int64_t R, int N, int n_fine, double* pts_out, float* ts_out, void* stream);
 
+/* ------------------------------------------------------------------ render paths
+ * Which kernels render a frame is the caller's explicit choice, resolved by ONE rule (tgtc_render_path), so that a ray's
+ * result never depends on the size of a buffer or on R:
+ *   TGTC_PATH_RAY_KERNEL  one launch of the persistent ray kernel (a wavefront owns a ray; per-sample tensors never exist;
+ *                         HBM sees 48 B of ray in and 16 B of pixel out); the workspace is not touched and may be NULL.
+ *                         Built when n_coarse and n_coarse+n_fine are multiples of 16 (32 in TGTC_PREC_FP16), n_coarse <= 192,
+ *                         n_coarse+n_fine <= 256, no coarse image is requested, and the precisions (coarse + fine) are
+ *                         fp16x3+fp16x3, fp16x3+fp16_fp6 or fp16+fp16 (plain), fp16x3 in all three handles (stylised).
+ *   TGTC_PATH_CHAIN       the same arithmetic as a sequence of per-sample kernels through `workspace` (device scratch of at
+ *                         least tgtc_render_workspace_bytes(R, n_coarse, n_fine) bytes); every shape and precision.
+ *                         For fp16x3 (coarse) + fp16_fp6 (fine) this is the split path: its fine pass runs ~10 % faster on
+ *                         the two-tile per-sample kernel (csrc/mlp_nerf_mx2.hip) than inside the ray kernel, and the
+ *                         per-sample tensors cost 0.3 % of the frame in HBM traffic.
+ *   TGTC_PATH_AUTO        the fastest: CHAIN for fp16x3 + fp16_fp6, otherwise RAY_KERNEL where it is built, otherwise CHAIN.
+ * tgtc_render_path is pure host code (no GPU needed): it returns the path `request` resolves to for these precisions
+ * (prec_style = -1 for the plain render), sample counts and want_coarse (nonzero: the coarse image is requested),
+ * TGTC_ERR_UNSUPPORTED when RAY_KERNEL is requested where it is not built, and TGTC_ERR_ARG for a bad enum or
+ * n_coarse < 3 or n_fine < 1. */
+#define TGTC_PATH_AUTO 0
+#define TGTC_PATH_RAY_KERNEL 1
+#define TGTC_PATH_CHAIN 2
+int tgtc_render_path(int request, int prec_coarse, int prec_fine, int prec_style, int n_coarse, int n_fine, int want_coarse);
+
 /* ------------------------------------------------------------------ fused plain render (cal_geometry chain)
  * rendering.py:27-51: coarse sample -> NeRF(coarse) -> composite -> fine sample -> NeRF(fine) -> composite.
  * jitter: float [R,n_coarse] or NULL.  Outputs: rgb float [R,3], depth float [R]; optional coarse outputs.
- *
- * tgtc_render_rays_plain runs the whole chain as ONE persistent kernel (a wavefront owns a ray; per-sample
- * tensors never exist; HBM sees 48 B of ray in and 16 B of pixel out) whenever
- *   - n_coarse and n_coarse+n_fine are multiples of 16 (32 in TGTC_PREC_FP16), n_coarse <= 192, total <= 256,
- *   - the precisions are fp16x3+fp16x3, fp16x3 (coarse) + fp16_fp6 (fine), or fp16+fp16,
- *   - the coarse image is not requested (rgb_coarse == t_coarse == NULL);
- * then `workspace` is not touched and may be NULL.  Otherwise it falls back to
- * tgtc_render_rays_plain_chain: the same arithmetic as a sequence of per-sample kernels through
- * workspace (device scratch of at least tgtc_render_workspace_bytes(R, n_coarse, n_fine) bytes).
- * One pair takes the chain by choice: fp16x3 (coarse) + fp16_fp6 (fine) with a sufficient workspace handed over -- its fine
- * pass runs ~10 % faster on the two-tile per-sample kernel (csrc/mlp_nerf_mx2.hip) than inside the ray kernel, and the
- * per-sample tensors cost 0.3 % of the frame in HBM traffic.  tgtc_render_rays_plain_fused is the single kernel and
- * nothing else (TGTC_ERR_UNSUPPORTED outside the conditions above). */
+ * path: a TGTC_PATH_* request, resolved by tgtc_render_path (errors are returned as it returns them).  A render that
+ * resolves to TGTC_PATH_CHAIN with a NULL or too small workspace returns TGTC_ERR_ARG; no path is ever switched for it. */
 size_t tgtc_render_workspace_bytes(int64_t R, int n_coarse, int n_fine);
 int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
-                           int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                           int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter, int path,
                            void* workspace, size_t workspace_bytes,
                            float* rgb_fine, float* t_fine, float* rgb_coarse, float* t_coarse, void* stream);
-int tgtc_render_rays_plain_chain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
-                                 const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_, float far_,
-                                 const float* jitter, void* workspace, size_t workspace_bytes, float* rgb_fine,
-                                 float* t_fine, float* rgb_coarse, float* t_coarse, void* stream);
-int tgtc_render_rays_plain_fused(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
-                                 const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_, float far_,
-                                 const float* jitter, float* rgb_fine, float* t_fine, void* stream);
 
 /* ------------------------------------------------------------------ a8: latent table
  * models.py:490-506 StyleLatents_variational.forward.  latents float [S,F,D] device, mu float [S,D] device,
@@ -182,21 +187,15 @@ int tgtc_style_mlp_forward(const tgtc_net* style, const float* x, const float* c
 int tgtc_styled_forward_rays(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
                              const float* ts, const float* z, int64_t R, int N, float* rgb, float* sigma, void* stream);
 /* The stylised render of rays (rendering.py:109-182 render_style): like tgtc_render_rays_plain with the stylised colour
- * (per-ray latent z float [R,32]).  tgtc_render_rays_styled runs it as ONE persistent kernel (a wavefront owns a ray; coarse
- * passes, fine sampling, concat MLP + NeRF trunk + style MLP per fine tile and compositing back to back; no per-sample
- * tensor, `workspace` not touched and may be NULL) whenever the three handles are TGTC_PREC_FP16X3, the sample counts
- * satisfy the rule of tgtc_render_rays_plain and the coarse image is not requested; otherwise it falls back to
- * tgtc_render_rays_styled_chain, the same arithmetic as a sequence of per-sample kernels through `workspace`. */
+ * (per-ray latent z float [R,32]) and the same `path` argument.  TGTC_PATH_RAY_KERNEL is ONE launch of the stylised ray
+ * kernel (coarse passes, fine sampling, concat MLP + NeRF trunk + style MLP per fine tile and compositing back to back);
+ * TGTC_PATH_CHAIN the same arithmetic as a sequence of per-sample kernels through `workspace` (its coarse passes and fine
+ * sampling are one launch of the plain ray kernel's first half where that is built and no coarse image is requested). */
 int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
                             const double* rays_o, const double* rays_d, const float* z, int64_t R, int n_coarse,
-                            int n_fine, float near_, float far_, const float* jitter, void* workspace,
+                            int n_fine, float near_, float far_, const float* jitter, int path, void* workspace,
                             size_t workspace_bytes, float* rgb_fine, float* t_fine, float* rgb_coarse,
                             float* t_coarse, void* stream);
-int tgtc_render_rays_styled_chain(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
-                                  const double* rays_o, const double* rays_d, const float* z, int64_t R, int n_coarse,
-                                  int n_fine, float near_, float far_, const float* jitter, void* workspace,
-                                  size_t workspace_bytes, float* rgb_fine, float* t_fine, float* rgb_coarse,
-                                  float* t_coarse, void* stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,67 @@ def test_no_gpu_calls_fail_loudly_or_are_pure():
             utils.alpha_composition(torch.zeros(2, 4, 3), torch.zeros(2, 4), torch.zeros(2, 4))
 
 
+def test_render_path_rule():
+    """tgtc_render_path (pure host code) against the rule it holds, written out here: every precision pair and style, sample
+    counts across and beyond the ray kernels' tiling limits, with and without the coarse image, all three requests; and
+    RayRenderer's queries of it against their former Python statements."""
+    import itertools
+
+    from tgtc_style_amd import hip, rendering
+    lib = hip.load()
+    AUTO, RAY, CHAIN = hip.PATH_AUTO, hip.PATH_RAY_KERNEL, hip.PATH_CHAIN
+    X3, F16, MX = hip.PREC_FP16X3, hip.PREC_FP16, hip.PREC_FP16_FP6
+    ERR_ARG, ERR_UNSUPPORTED = -1, -2
+
+    def built(pc, pf, ps, nc, nf, want_coarse):
+        precs = (pc, pf) in ((X3, X3), (X3, MX), (F16, F16)) if ps == -1 else pc == pf == ps == X3
+        step = 32 if pc == F16 else 16
+        return (precs and not want_coarse and nf >= 1 and nc >= 16 and nc % step == 0 and (nc + nf) % step == 0 and nc <= 192
+                and nc + nf <= 256)
+
+    def expected(request, pc, pf, ps, nc, nf, want_coarse):
+        if nc < 3 or nf < 1:
+            return ERR_ARG
+        b = built(pc, pf, ps, nc, nf, want_coarse)
+        if request == RAY:
+            return RAY if b else ERR_UNSUPPORTED
+        if request == CHAIN:
+            return CHAIN
+        return RAY if b and (pc, pf) != (X3, MX) else CHAIN    # AUTO: the split path for fp16x3 + fp16mx
+
+    precs = (X3, F16, MX)
+    n_coarse = (-16, 0, 2, 3, 8, 15, 16, 17, 24, 32, 48, 64, 100, 128, 160, 176, 192, 193, 208, 224, 256, 272)
+    n_fine = (-1, 0, 1, 8, 15, 16, 28, 32, 48, 64, 65, 80, 96, 128, 192, 240, 256)
+    n = 0
+    for request, pc, pf, ps, nc, nf, wc in itertools.product((AUTO, RAY, CHAIN), precs, precs, (-1,) + precs, n_coarse, n_fine,
+                                                             (0, 1)):
+        got = lib.tgtc_render_path(request, pc, pf, ps, nc, nf, wc)
+        assert got == expected(request, pc, pf, ps, nc, nf, wc), (request, pc, pf, ps, nc, nf, wc, got)
+        n += got == RAY
+    assert n > 100     # the grid reaches every ray kernel
+    for bad in ((3, X3, X3, -1), (-1, X3, X3, -1), (AUTO, 3, X3, -1), (AUTO, X3, -1, -1), (AUTO, X3, X3, -2), (AUTO, X3, X3, 3)):
+        assert lib.tgtc_render_path(*bad, 128, 64, 0) == ERR_ARG, bad
+
+    class Packed:      # RayRenderer only reads .packed().precision to choose a path
+        def __init__(self, precision):
+            self.precision = precision
+
+        def packed(self):
+            return self
+
+    names = ("fp16x3", "fp16", "fp16mx")
+    for c, f, st in itertools.product(names, names, names):
+        r = rendering.RayRenderer(Packed(c), Packed(f), Packed(st))
+        assert r._split_is_faster() == ((c, f) == ("fp16x3", "fp16mx"))
+        step = 32 if c == "fp16" else 16
+        pair = (c, f) in (("fp16x3", "fp16x3"), ("fp16x3", "fp16mx"), ("fp16", "fp16"))
+        for nc, nf in itertools.product(n_coarse, n_fine):
+            old = (pair and nf >= 1 and nc >= 16 and nc % step == 0 and (nc + nf) % step == 0 and nc <= 192
+                   and nc + nf <= 256)
+            assert r._fused_shape(nc, nf) == old, (c, f, nc, nf)
+            assert r._fused_styled_shape(nc, nf) == ({c, f, st} == {"fp16x3"} and old), (c, f, st, nc, nf)
+
+
 def test_llff_poses_golden(golden):
     """llff_poses (host numpy, like the reference) against the reference's own load_llff_data run on a synthetic scene
     directory (g11): recentred poses, rescaled bounds, the 120-view spiral, hold-out index, cps_valid."""

@@ -36,6 +36,10 @@ int fail(int code, const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// CU count of the current device, queried at every call (nothing cached: it follows hipSetDevice).  The persistent
+// kernels launch one workgroup per CU at most.
+int cu_count(int& cus);
+
 constexpr int kWave = 64;
 
 }  // namespace tgtc

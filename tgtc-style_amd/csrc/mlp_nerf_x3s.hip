@@ -83,13 +83,8 @@ __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long 
 
 int nerf_x3s_launch(const NerfArgs& a, hipStream_t st) {
     using C = CfgX3s;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        TGTC_HIP_CHECK(hipGetDevice(&dev));
-        TGTC_HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        cus = n > 0 ? n : 256;
-    }
+    int cus = 0;
+    if (const int rc = cu_count(cus)) return rc;
     const long long n_pass = (a.M + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;
     nerf_x3s_kernel<<<(unsigned)(n_pass < cus ? n_pass : cus), C::NWAVES * 64, 0, st>>>(a, n_pass);
     TGTC_LAUNCH_CHECK();

@@ -467,9 +467,8 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
     for (int i = 0; i < 8; ++i)
         if (ps.frag0[i] != style_frag0(i) || ps.bias0[i] != style_bias0(i))
             return fail(TGTC_ERR_UNSUPPORTED, "style_create: internal layout mismatch at style layer %d", i);
-    int dev = 0, n_cu = 256;
-    TGTC_HIP_CHECK(hipGetDevice(&dev));
-    TGTC_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    int n_cu = 0;
+    if (const int rc = cu_count(n_cu)) return rc;
     tgtc_net* net = new tgtc_net();
     net->kind = 1, net->precision = precision;
     net->bias_bytes = kStylePairBiasBytes;

@@ -51,52 +51,55 @@ extern "C" size_t tgtc_render_workspace_bytes(int64_t R, int n_coarse, int n_fin
     return RenderWorkspace(nullptr, R, n_coarse, n_fine).total;
 }
 
-// The plain render.  Whenever the sample counts and precisions allow it (and the caller does not ask for the coarse
-// image) this is ONE launch of the fused ray kernel (render_fused.hip) and the workspace is not touched; otherwise
-// the chain of per-sample kernels below runs (tgtc_render_rays_plain_chain, always available).
-extern "C" int tgtc_render_rays_plain_fused(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
-                                            const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_,
-                                            float far_, const float* jitter, float* rgb_fine, float* t_fine, void* stream) {
-    TGTC_REQUIRE(coarse && fine && R >= 0, "render_rays_plain_fused: bad argument");
-    if (!(coarse->kind == 0 && fine->kind == 0 && fused_render_supports(coarse->precision, fine->precision, n_coarse, n_fine)))
-        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_plain_fused: no single-kernel build for precisions %d + %d with %d + %d samples",
-                    coarse->precision, fine->precision, n_coarse, n_fine);
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && rgb_fine && t_fine, "render_rays_plain_fused: null pointer");
-    FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, fine->dev, rgb_fine, t_fine, nullptr};
-    return launch_fused_render(coarse->precision, fine->precision, a, as_stream(stream));
+// Is there a ray kernel for this render?  prec_s < 0: the plain kernel (render_fused.hip); otherwise the stylised one
+// (render_styled_fused.hip), built for fp16x3 in all three handles.  The tiling limits are those of the per-wave LDS strip.
+static bool ray_kernel_built(int prec_c, int prec_f, int prec_s, int n_coarse, int n_fine, int want_coarse) {
+    const bool precs = prec_s < 0 ? (prec_c == TGTC_PREC_FP16X3 && (prec_f == TGTC_PREC_FP16X3 || prec_f == TGTC_PREC_FP16_FP6)) ||
+                                        (prec_c == TGTC_PREC_FP16 && prec_f == TGTC_PREC_FP16)
+                                  : prec_c == TGTC_PREC_FP16X3 && prec_f == TGTC_PREC_FP16X3 && prec_s == TGTC_PREC_FP16X3;
+    const int step = prec_c == TGTC_PREC_FP16 ? 32 : 16;   // tiles per pass x 16 samples
+    return precs && !want_coarse && n_fine >= 1 && n_coarse >= 16 && n_coarse % step == 0 && (n_coarse + n_fine) % step == 0 &&
+           n_coarse <= kFusedMaxCoarse && n_coarse + n_fine <= kFusedMaxTotal;
 }
 
+extern "C" int tgtc_render_path(int request, int prec_coarse, int prec_fine, int prec_style, int n_coarse, int n_fine,
+                                int want_coarse) {
+    auto prec_ok = [](int p) { return p == TGTC_PREC_FP16X3 || p == TGTC_PREC_FP16 || p == TGTC_PREC_FP16_FP6; };
+    TGTC_REQUIRE(request == TGTC_PATH_AUTO || request == TGTC_PATH_RAY_KERNEL || request == TGTC_PATH_CHAIN,
+                 "render_path: bad request %d", request);
+    TGTC_REQUIRE(prec_ok(prec_coarse) && prec_ok(prec_fine) && (prec_style == -1 || prec_ok(prec_style)),
+                 "render_path: bad precision %d / %d / %d", prec_coarse, prec_fine, prec_style);
+    // the reference dereferences None when N_samples_fine == 0 (SURVEY Q1/Q2); require it instead
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    const bool built = ray_kernel_built(prec_coarse, prec_fine, prec_style, n_coarse, n_fine, want_coarse);
+    if (request == TGTC_PATH_RAY_KERNEL && !built)
+        return fail(TGTC_ERR_UNSUPPORTED, "render: no ray kernel for precisions %d + %d (style %d), %d + %d samples%s",
+                    prec_coarse, prec_fine, prec_style, n_coarse, n_fine, want_coarse ? ", coarse image" : "");
+    // fp16x3 + fp16_fp6: the fine pass is faster on the two-tile per-sample kernel (mlp_nerf_mx2.hip: half the LDS bytes per
+    // MFMA of any one-tile loop, the ray kernel's included) than inside the ray kernel, and the per-sample tensors it
+    // needs are 0.3 % of the frame time in HBM traffic: AUTO takes the chain (the split path)
+    const bool split = prec_coarse == TGTC_PREC_FP16X3 && prec_fine == TGTC_PREC_FP16_FP6;
+    if (request == TGTC_PATH_AUTO) return built && !split ? TGTC_PATH_RAY_KERNEL : TGTC_PATH_CHAIN;
+    return request;
+}
+
+// The plain render: ONE launch of the fused ray kernel (render_fused.hip; the workspace is not touched) or the chain of
+// per-sample kernels through the workspace, as `path` resolves.
 extern "C" int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
                                       const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_,
-                                      float far_, const float* jitter, void* workspace, size_t workspace_bytes,
+                                      float far_, const float* jitter, int path, void* workspace, size_t workspace_bytes,
                                       float* rgb_fine, float* t_fine, float* rgb_coarse, float* t_coarse,
                                       void* stream) {
     TGTC_REQUIRE(coarse && fine && R >= 0, "render_rays_plain: bad argument");
-    if (!rgb_coarse && !t_coarse && coarse->kind == 0 && fine->kind == 0 &&
-        fused_render_supports(coarse->precision, fine->precision, n_coarse, n_fine)) {
-        // fp16x3 + fp16_fp6: the fine pass is faster on the two-tile per-sample kernel (mlp_nerf_mx2.hip: half the LDS bytes per
-        // MFMA of any one-tile loop, the ray kernel's included) than inside the ray kernel, and the per-sample tensors it
-        // needs are 0.3 % of the frame time in HBM traffic: a caller that hands over the workspace gets the split path
-        const bool split_is_faster = coarse->precision == TGTC_PREC_FP16X3 && fine->precision == TGTC_PREC_FP16_FP6 && workspace &&
-                                     workspace_bytes >= tgtc_render_workspace_bytes(R, n_coarse, n_fine);
-        if (!split_is_faster)
-            return tgtc_render_rays_plain_fused(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, rgb_fine, t_fine, stream);
-    }
-    return tgtc_render_rays_plain_chain(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, workspace,
-                                        workspace_bytes, rgb_fine, t_fine, rgb_coarse, t_coarse, stream);
-}
-
-extern "C" int tgtc_render_rays_plain_chain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
-                                            const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_,
-                                            float far_, const float* jitter, void* workspace, size_t workspace_bytes,
-                                            float* rgb_fine, float* t_fine, float* rgb_coarse, float* t_coarse,
-                                            void* stream) {
-    TGTC_REQUIRE(coarse && fine && R >= 0, "render_rays_plain: bad argument");
-    // the reference dereferences None when N_samples_fine == 0 (SURVEY Q1/Q2); require it instead
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render_rays_plain: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)",
-                 n_coarse, n_fine);
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0, "render_rays_plain: coarse and fine must be NeRF handles");
+    path = tgtc_render_path(path, coarse->precision, fine->precision, -1, n_coarse, n_fine, rgb_coarse || t_coarse);
+    if (path < 0) return path;
     if (R == 0) return TGTC_OK;
+    if (path == TGTC_PATH_RAY_KERNEL) {
+        TGTC_REQUIRE(rays_o && rays_d && rgb_fine && t_fine, "render_rays_plain: null pointer");
+        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, fine->dev, rgb_fine, t_fine, nullptr};
+        return launch_fused_render(coarse->precision, fine->precision, a, as_stream(stream));
+    }
     TGTC_REQUIRE(rays_o && rays_d && workspace && rgb_fine && t_fine, "render_rays_plain: null pointer");
     RenderWorkspace ws(static_cast<char*>(workspace), R, n_coarse, n_fine);
     TGTC_REQUIRE(workspace_bytes >= ws.total, "render_rays_plain: workspace of %zu bytes, need %zu", workspace_bytes,
@@ -117,18 +120,25 @@ extern "C" int tgtc_render_rays_plain_chain(const tgtc_net* coarse, const tgtc_n
     return launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, n_coarse + n_fine, rgb_fine, t_fine, nullptr, st);
 }
 
-// rendering.py:118-178 (render_style).  Whenever the sample counts and precisions allow it (fp16x3 everywhere) and the caller
-// does not ask for the coarse image this is ONE launch of the stylised ray kernel (render_styled_fused.hip) and the workspace is
-// not touched; otherwise the chain of per-sample kernels below runs (tgtc_render_rays_styled_chain, always available).
+// rendering.py:118-178 (render_style): ONE launch of the stylised ray kernel (render_styled_fused.hip; the workspace is not
+// touched) or the stylised chain of per-sample kernels through the workspace, as `path` resolves.  The chain is the plain
+// one with the stylised colour on both passes.  The coarse colours only matter if the caller asks for the coarse image: the
+// fine sampler consumes the weights, which depend on sigma alone, so by default the coarse pass runs the sigma-only NeRF
+// kernel -- or, where the plain ray kernel is built for the coarse precision, its first half (coarse depths -> coarse sigma
+// -> weights -> fine depths, which then never leave the ray kernel).
 extern "C" int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
                                        const double* rays_o, const double* rays_d, const float* z, int64_t R,
-                                       int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                       int n_coarse, int n_fine, float near_, float far_, const float* jitter, int path,
                                        void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
                                        float* rgb_coarse, float* t_coarse, void* stream) {
     TGTC_REQUIRE(coarse && fine && style && R >= 0, "render_rays_styled: bad argument");
-    if (!rgb_coarse && !t_coarse && coarse->kind == 0 && fine->kind == 0 && style->kind == 1 &&
-        fused_styled_supports(coarse->precision, fine->precision, style->precision, n_coarse, n_fine)) {
-        if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "render_rays_styled: coarse and fine must be NeRF handles, style a style handle");
+    const int want_coarse = rgb_coarse || t_coarse;
+    path = tgtc_render_path(path, coarse->precision, fine->precision, style->precision, n_coarse, n_fine, want_coarse);
+    if (path < 0) return path;
+    if (R == 0) return TGTC_OK;
+    if (path == TGTC_PATH_RAY_KERNEL) {
         TGTC_REQUIRE(rays_o && rays_d && z && rgb_fine && t_fine, "render_rays_styled: null pointer");
         FusedStyledArgs a{};
         a.ray = FusedArgs{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, fine->dev, rgb_fine, t_fine, nullptr};
@@ -136,30 +146,13 @@ extern "C" int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* f
         a.style_stream = style->dev + style->stream2_off, a.slab = style->dev + style->stash_off;
         return launch_fused_styled(coarse->precision, a, style->n_wg, as_stream(stream));
     }
-    return tgtc_render_rays_styled_chain(coarse, fine, style, rays_o, rays_d, z, R, n_coarse, n_fine, near_, far_, jitter, workspace,
-                                         workspace_bytes, rgb_fine, t_fine, rgb_coarse, t_coarse, stream);
-}
-
-// The stylised chain of per-sample kernels: like the plain chain, with the stylised colour on both passes.
-// The coarse colours only matter if the caller asks for the coarse image: the fine sampler consumes the
-// weights, which depend on sigma alone, so by default the coarse pass runs the sigma-only NeRF kernel.
-extern "C" int tgtc_render_rays_styled_chain(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
-                                             const double* rays_o, const double* rays_d, const float* z, int64_t R,
-                                             int n_coarse, int n_fine, float near_, float far_, const float* jitter,
-                                             void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
-                                             float* rgb_coarse, float* t_coarse, void* stream) {
-    TGTC_REQUIRE(coarse && fine && style && R >= 0, "render_rays_styled: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render_rays_styled: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)",
-                 n_coarse, n_fine);
-    if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled: null pointer");
     RenderWorkspace ws(static_cast<char*>(workspace), R, n_coarse, n_fine);
     TGTC_REQUIRE(workspace_bytes >= ws.total, "render_rays_styled: workspace of %zu bytes, need %zu", workspace_bytes,
                  ws.total);
     hipStream_t st = as_stream(stream);
     int rc;
-    if (!rgb_coarse && !t_coarse && coarse->kind == 0 && fused_depths_supports(coarse->precision, n_coarse, n_fine)) {
-        // no coarse image wanted: coarse depths -> coarse sigma -> weights -> fine depths never leave the ray kernel
+    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, want_coarse)) {
         FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
         rc = launch_fused_depths(coarse->precision, a, st);
         if (rc) return rc;

@@ -5,6 +5,9 @@
 
 namespace tgtc {
 
+constexpr int kFusedMaxCoarse = 192;   // Nc supported by the per-wave LDS strip of the ray kernels (weights / cdf)
+constexpr int kFusedMaxTotal = 256;    // Nc + Nf (depths)
+
 struct FusedArgs {
     const double* rays_o;
     const double* rays_d;
@@ -28,11 +31,9 @@ struct FusedStyledArgs {
     char* slab;                 // n_wg * kStashBytesPerWG
 };
 
+// which calls they take is decided by tgtc_render_path (render.hip) alone
 int launch_fused_render(int prec_c, int prec_f, const FusedArgs& a, hipStream_t st);
-bool fused_render_supports(int prec_c, int prec_f, int n_coarse, int n_fine);
 int launch_fused_depths(int prec_c, const FusedArgs& a, hipStream_t st);
-bool fused_depths_supports(int prec_c, int n_coarse, int n_fine);
 int launch_fused_styled(int prec_c, const FusedStyledArgs& a, int n_wg, hipStream_t st);
-bool fused_styled_supports(int prec_c, int prec_f, int prec_style, int n_coarse, int n_fine);
 
 }  // namespace tgtc

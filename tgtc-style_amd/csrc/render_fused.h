@@ -19,8 +19,7 @@ namespace tgtc {
 
 
 constexpr int kFusedDepthsOnly = -1;                      // PF of the kernel that stops after the fine sampling (stylised render)
-constexpr int kFusedMaxTotal = 256;                       // Nc + Nf supported by the per-wave LDS strip
-constexpr int kFusedStripBytes = (kFusedMaxTotal + 192 + 8) * 4;   // depths | weights / cdf (Nc <= 192) | compositing state
+constexpr int kFusedStripBytes = (kFusedMaxTotal + kFusedMaxCoarse + 8) * 4;   // depths | weights / cdf | compositing state
 
 // Geometry per precision: 8 waves = 2 per SIMD (mlp_nerf.hip CfgFast / CfgExact, mlp_nerf_mx.hip CfgMx)
 // (SLOTS: 16 KiB ring slots; the stylised kernel gives one up for its second bias table)
@@ -134,6 +133,6 @@ __device__ __forceinline__ void fused_pass(char* smem, int wave, int lane, const
 }
 
 // per-wave LDS strip: depths | weights / cdf | compositing state
-constexpr int kStripAll = 0, kStripW = kFusedMaxTotal, kStripAcc = kFusedMaxTotal + 192;
+constexpr int kStripAll = 0, kStripW = kFusedMaxTotal, kStripAcc = kFusedMaxTotal + kFusedMaxCoarse;
 
 }  // namespace tgtc

@@ -189,9 +189,8 @@ __global__ void __launch_bounds__(512, 2) fused_render_kernel(FusedArgs a) {
 }
 
 int launch_fused_render(int prec_c, int prec_f, const FusedArgs& a, hipStream_t st) {
-    int dev = 0, cus = 0;
-    TGTC_HIP_CHECK(hipGetDevice(&dev));
-    TGTC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int cus = 0;
+    if (const int rc = cu_count(cus)) return rc;
     const long long groups = (a.R + 7) / 8;
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
     if (prec_c == TGTC_PREC_FP16X3 && prec_f == TGTC_PREC_FP16X3)
@@ -209,9 +208,8 @@ int launch_fused_render(int prec_c, int prec_f, const FusedArgs& a, hipStream_t 
 // Coarse passes + fine sampling of the fused kernel alone: ts_out[R, NC + NF] = the merged depths the fine pass is evaluated
 // at (rendering.py:118-160 up to the second sample_pdf; the stylised fine pass then runs mlp_style.hip's kernel on them).
 int launch_fused_depths(int prec_c, const FusedArgs& a, hipStream_t st) {
-    int dev = 0, cus = 0;
-    TGTC_HIP_CHECK(hipGetDevice(&dev));
-    TGTC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int cus = 0;
+    if (const int rc = cu_count(cus)) return rc;
     const long long groups = (a.R + 7) / 8;
     const unsigned grid = (unsigned)(groups < cus ? groups : cus);
     if (prec_c == TGTC_PREC_FP16X3)
@@ -222,18 +220,6 @@ int launch_fused_depths(int prec_c, const FusedArgs& a, hipStream_t st) {
         return fail(TGTC_ERR_UNSUPPORTED, "fused depths: no kernel for coarse precision %d", prec_c);
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;
-}
-bool fused_depths_supports(int prec_c, int n_coarse, int n_fine) {
-    return fused_render_supports(prec_c, prec_c, n_coarse, n_fine);
-}
-
-// can the fused kernel take this call?  (otherwise render.hip runs the chain of per-sample kernels)
-bool fused_render_supports(int prec_c, int prec_f, int n_coarse, int n_fine) {
-    const bool pair = (prec_c == TGTC_PREC_FP16X3 && (prec_f == TGTC_PREC_FP16X3 || prec_f == TGTC_PREC_FP16_FP6)) ||
-                      (prec_c == TGTC_PREC_FP16 && prec_f == TGTC_PREC_FP16);
-    const int step = prec_c == TGTC_PREC_FP16 ? 32 : 16;   // tiles per pass x 16 samples
-    return pair && n_fine >= 1 && n_coarse >= 16 && n_coarse % step == 0 && (n_coarse + n_fine) % step == 0 && n_coarse <= 192 &&
-           n_coarse + n_fine <= kFusedMaxTotal;
 }
 
 }  // namespace tgtc

@@ -300,10 +300,4 @@ int launch_fused_styled(int prec_c, const FusedStyledArgs& a, int n_wg, hipStrea
     return TGTC_OK;
 }
 
-// can the stylised ray kernel take this call?  (otherwise render.hip runs the per-sample chain)
-bool fused_styled_supports(int prec_c, int prec_f, int prec_style, int n_coarse, int n_fine) {
-    return prec_c == TGTC_PREC_FP16X3 && prec_f == TGTC_PREC_FP16X3 && prec_style == TGTC_PREC_FP16X3 &&
-           fused_render_supports(prec_c, prec_f, n_coarse, n_fine);
-}
-
 }  // namespace tgtc

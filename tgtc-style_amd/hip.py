@@ -18,6 +18,10 @@ PREC_FP16 = 1     # single fp16 MFMA product (fast mode)
 PREC_FP16_FP6 = 2  # fp16 product + two block-scaled fp6 correction products (NeRF nets only)
 PRECISIONS = {"fp16x3": PREC_FP16X3, "fp16": PREC_FP16, "fp16mx": PREC_FP16_FP6}
 
+PATH_AUTO = 0         # tgtc_render_path: the library's fastest path for the render
+PATH_RAY_KERNEL = 1   # one launch of the persistent ray kernel, no workspace
+PATH_CHAIN = 2        # per-sample kernels through the workspace (the split path for coarse fp16x3 + fine fp16mx)
+
 _lib = None
 
 c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -50,12 +54,9 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p],
     "tgtc_sample_fine": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "tgtc_render_workspace_bytes": [c_int64, c_int, c_int],
+    "tgtc_render_path": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "tgtc_render_rays_plain": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float,
-                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tgtc_render_rays_plain_chain": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float,
-                                     c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tgtc_render_rays_plain_fused": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float,
-                                     c_void_p, c_void_p, c_void_p, c_void_p],
+                               c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_image_epilogue": [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p],
     "tgtc_latents_forward": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_float, c_int,
                              c_void_p, c_void_p],
@@ -69,11 +70,8 @@ _OPTIONAL = {
     "tgtc_styled_forward_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                  c_void_p, c_void_p, c_void_p],
     "tgtc_render_rays_styled": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p],
-    "tgtc_render_rays_styled_chain": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                      c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p],
+                                c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p],
 }
 
 

@@ -23,33 +23,37 @@ class RayRenderer:
     """
 
     def __init__(self, coarse, fine, style=None, fused=True):
-        """fused=True: the library's fastest path -- a single persistent ray kernel where one is built, except for coarse
-        fp16x3 + fine fp16mx, whose fine pass runs faster on the two-tile per-sample kernel (include/tgtc_hip.h,
-        tgtc_render_rays_plain: the split path, taken when the workspace is handed over).  fused="single" asks for the single
-        kernel and nothing else (tgtc_render_rays_plain_fused; plain renders only).  fused=False forces the chain of
-        per-sample kernels (tgtc_render_rays_plain_chain / tgtc_render_rays_styled_chain).  All three agree to rounding, the
-        network arithmetic bit for bit (tests/test_fused_gpu.py)."""
+        """fused=True: the library's fastest path (TGTC_PATH_AUTO) -- a single persistent ray kernel where one is built, except
+        for coarse fp16x3 + fine fp16mx, whose fine pass runs faster on the two-tile per-sample kernel (the split path).
+        fused="single" asks for the single ray kernel and nothing else (TGTC_PATH_RAY_KERNEL).  fused=False forces the chain
+        of per-sample kernels (TGTC_PATH_CHAIN).  All three agree to rounding, the network arithmetic bit for bit
+        (tests/test_fused_gpu.py).  include/tgtc_hip.h, tgtc_render_path, holds the rule."""
         if fused not in (True, False, "single"):
             raise ValueError("fused must be True, False or 'single'")
         self.coarse, self.fine, self.style, self.fused = coarse, fine, style, fused
         self._ws = None
 
+    _REQUEST = {True: hip.PATH_AUTO, "single": hip.PATH_RAY_KERNEL, False: hip.PATH_CHAIN}
+
+    def _path(self, nc, nf, request=None, styled=False, want_coarse=False):
+        """The path the library resolves `request` (default: this renderer's `fused`) to, or its error code (< 0)."""
+        request = self._REQUEST[self.fused] if request is None else request
+        pc, pf = (hip.PRECISIONS[n.packed().precision] for n in (self.coarse, self.fine))
+        ps = hip.PRECISIONS[self.style.packed().precision] if styled else -1
+        return hip.load().tgtc_render_path(request, pc, pf, ps, nc, nf, int(want_coarse))
+
     def _split_is_faster(self):
-        """Mirror of the library's rule (csrc/render.hip, tgtc_render_rays_plain)."""
-        return (self.coarse.packed().precision, self.fine.packed().precision) == ("fp16x3", "fp16mx")
+        """Does the library's fastest path take the per-sample kernels although a ray kernel is built?  (The rule does not
+        depend on the sample counts then; 64 + 64 is a shape every ray kernel takes.)"""
+        return self._fused_shape(64, 64) and self._path(64, 64, hip.PATH_AUTO) == hip.PATH_CHAIN
 
     def _fused_shape(self, nc, nf):
-        """Mirror of the library's rule (include/tgtc_hip.h, tgtc_render_rays_plain): when it renders with the single
-        fused kernel no workspace is needed."""
-        pc, pf = self.coarse.packed().precision, self.fine.packed().precision
-        pair = (pc, pf) in (("fp16x3", "fp16x3"), ("fp16x3", "fp16mx"), ("fp16", "fp16"))
-        step = 32 if pc == "fp16" else 16
-        return pair and nf >= 1 and nc >= 16 and nc % step == 0 and (nc + nf) % step == 0 and nc <= 192 and nc + nf <= 256
+        """Is the single ray kernel of the plain render built for these sample counts and precisions?"""
+        return self._path(nc, nf, hip.PATH_RAY_KERNEL) == hip.PATH_RAY_KERNEL
 
     def _fused_styled_shape(self, nc, nf):
-        """The same for tgtc_render_rays_styled: the stylised ray kernel is built for fp16x3 in all three handles."""
-        precs = {self.coarse.packed().precision, self.fine.packed().precision, self.style.packed().precision}
-        return precs == {"fp16x3"} and self._fused_shape(nc, nf)
+        """The same for the stylised render (its ray kernel takes the three handles' precisions)."""
+        return self._path(nc, nf, hip.PATH_RAY_KERNEL, styled=True) == hip.PATH_RAY_KERNEL
 
     def _workspace(self, R, nc, nf, device):
         need = hip.load().tgtc_render_workspace_bytes(R, nc, nf)
@@ -67,36 +71,29 @@ class RayRenderer:
         rays_d = rays_d.to(torch.float64).contiguous()
         R, dev = rays_o.shape[0], rays_o.device
         plain = self.style is None or z is None
-        one_kernel = self.fused and not want_coarse and (self._fused_shape(n_coarse, n_fine) if plain else
-                                                         self._fused_styled_shape(n_coarse, n_fine))
-        if self.fused == "single":
-            if not (plain and one_kernel):
-                raise ValueError("fused='single': no single-kernel build for this render (precisions, sample counts, coarse image or style)")
-        elif one_kernel and plain and self._split_is_faster():
-            one_kernel = False              # hand the workspace over: the library takes the split path
-        ws = None if one_kernel else self._workspace(R, n_coarse, n_fine, dev)
+        path = self._path(n_coarse, n_fine, styled=not plain, want_coarse=want_coarse)
+        if path < 0:
+            if self.fused == "single":
+                raise ValueError("fused='single': no single-kernel build for this render (precisions, sample counts or coarse image)")
+            hip.check(path)
+        ws = self._workspace(R, n_coarse, n_fine, dev) if path == hip.PATH_CHAIN else None
         rgb = torch.empty(R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
         rgb_c = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_coarse else None
         t_c = torch.empty(R, device=dev, dtype=torch.float32) if want_coarse else None
         if jitter is not None:
             jitter = jitter.to(torch.float32).contiguous()
-        if plain and self.fused == "single":
-            hip.check(lib.tgtc_render_rays_plain_fused(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o),
-                                                       hip.ptr(rays_d), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
-                                                       hip.ptr(rgb), hip.ptr(t), hip.stream()))
-        elif plain:
-            fn = lib.tgtc_render_rays_plain if self.fused else lib.tgtc_render_rays_plain_chain
-            hip.check(fn(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), R,
-                         n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), hip.ptr(ws),
-                         0 if ws is None else ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(rgb_c), hip.ptr(t_c),
-                         hip.stream()))
+        rest = (path, hip.ptr(ws), 0 if ws is None else ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(rgb_c), hip.ptr(t_c),
+                   hip.stream())
+        if plain:
+            hip.check(lib.tgtc_render_rays_plain(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o),
+                                                 hip.ptr(rays_d), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
+                                                 *rest))
         else:
             z = z.to(torch.float32).contiguous()
-            fn = lib.tgtc_render_rays_styled if self.fused else lib.tgtc_render_rays_styled_chain
-            hip.check(fn(self.coarse.packed().handle, self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o),
-                         hip.ptr(rays_d), hip.ptr(z), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), hip.ptr(ws),
-                         0 if ws is None else ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(rgb_c), hip.ptr(t_c), hip.stream()))
+            hip.check(lib.tgtc_render_rays_styled(self.coarse.packed().handle, self.fine.packed().handle,
+                                                  self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(z), R,
+                                                  n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), *rest))
         out = {"rgb": rgb, "t": t}
         if want_coarse:
             out["rgb_coarse"], out["t_coarse"] = rgb_c, t_c
