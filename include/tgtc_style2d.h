@@ -67,13 +67,17 @@ int tgtc_s2d_decoder_layer(const tgtc_style2d* h, const char* prefix, const floa
                            int S, const float* query_pos, void* workspace, size_t workspace_bytes, float* out,
                            void* stream);
 
-/* a18  CNN decoder (tctrans.py:36-66): tokens [h*w,512] -> image [3, 8h, 8w]. */
+/* a18  CNN decoder (tctrans.py:36-66): tokens [h*w,512] -> image [3, 8h, 8w].
+ * Requires h >= 2 and w >= 2: ReflectionPad(1) needs a second row and column to mirror (PyTorch refuses a 1-wide map
+ * the same way); anything smaller returns TGTC_ERR_ARG before a kernel is launched. */
 size_t tgtc_s2d_decode_workspace_bytes(int h, int w);
 int tgtc_s2d_cnn_decode(const tgtc_style2d* hd, const float* tokens, int h, int w, void* workspace,
                         size_t workspace_bytes, float* image, void* stream);
 
 /* a19  StyTrans.encode_with_intermediate over vgg[:31] (tctrans.py:161-166): img [3,H,W] -> relu1_1 [64,H,W],
- * relu2_1 [128,ceil(H/2),ceil(W/2)], relu3_1 [256,..], relu4_1 [512,..] (NCHW).  Any output may be NULL. */
+ * relu2_1 [128,ceil(H/2),ceil(W/2)], relu3_1 [256,..], relu4_1 [512,..] (NCHW).  Any output may be NULL.
+ * Requires H >= 9 and W >= 9, so that the map entering relu4_1's reflection padding (three ceil-mode pools later) still
+ * has 2 rows and columns; anything smaller returns TGTC_ERR_ARG before a kernel is launched. */
 size_t tgtc_s2d_vgg_workspace_bytes(int H, int W);
 int tgtc_s2d_vgg_encode(const tgtc_style2d* h, const float* img, int H, int W, void* workspace,
                         size_t workspace_bytes, float* relu1_1, float* relu2_1, float* relu3_1, float* relu4_1,

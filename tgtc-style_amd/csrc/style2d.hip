@@ -1279,6 +1279,8 @@ extern "C" size_t tgtc_s2d_decode_workspace_bytes(int h, int w) {
 extern "C" int tgtc_s2d_cnn_decode(const tgtc_style2d* hd, const float* tokens, int h, int w, void* workspace,
                                    size_t workspace_bytes, float* image, void* stream) {
     TGTC_REQUIRE(hd && h > 0 && w > 0 && tokens && workspace && image, "cnn_decode: bad argument");
+    // ReflectionPad(1) mirrors row -1 onto row 1: a map one token high or wide has no such row (PyTorch refuses it too)
+    TGTC_REQUIRE(h >= 2 && w >= 2, "cnn_decode: %d x %d tokens, reflection padding needs h >= 2 and w >= 2", h, w);
     TGTC_REQUIRE(workspace_bytes >= tgtc_s2d_decode_workspace_bytes(h, w), "cnn_decode: workspace too small");
     hipStream_t st = as_stream(stream);
     const size_t half = workspace_bytes / 2 & ~(size_t)255;
@@ -1315,6 +1317,8 @@ extern "C" int tgtc_s2d_vgg_encode(const tgtc_style2d* h, const float* img, int 
                                    size_t workspace_bytes, float* relu1_1, float* relu2_1, float* relu3_1,
                                    float* relu4_1, void* stream) {
     TGTC_REQUIRE(h && H > 0 && W > 0 && img && workspace, "vgg_encode: bad argument");
+    // every 3x3 convolution up to relu4_1 must see at least 2 rows and columns: ceil(ceil(ceil(H/2)/2)/2) >= 2
+    TGTC_REQUIRE(H >= 9 && W >= 9, "vgg_encode: %d x %d image, reflection padding at relu4_1 needs H >= 9 and W >= 9", H, W);
     TGTC_REQUIRE(workspace_bytes >= tgtc_s2d_vgg_workspace_bytes(H, W), "vgg_encode: workspace too small");
     hipStream_t st = as_stream(stream);
     const size_t third = workspace_bytes / 3 & ~(size_t)255;
