@@ -197,6 +197,42 @@ int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* fine, const 
                             size_t workspace_bytes, float* rgb_fine, float* t_fine, float* rgb_coarse,
                             float* t_coarse, void* stream);
 
+/* ------------------------------------------------------------------ K latent sets per ray, shared geometry
+ * The same rays under K latents (the styles of one frame, a --sigma_scale sweep, a style transition).  In the stylised
+ * chain the latent enters only the concat MLP and the style MLP; the coarse pass, the fine depths, the fine NeRF trunk
+ * (sigma, base_remap), hence the compositing weights and the depth, are functions of the ray alone and are computed ONCE:
+ * per ray at 128 + 64 samples 169.8 M multiply-accumulates are shared and 182.4 M are per latent, K latents cost
+ * 169.8 + K x 182.4 instead of K x 352.2.  All K images have the same sample positions and bit-identical depth.
+ *
+ * Layouts:  z float [K,R,32];  rgb float [K,R,N,3];  sigma float [R,N] (one plane, may be NULL);
+ *           rgb_fine float [K,R,3];  t_fine float [R].
+ * Identity: per latent the kernel performs the MFMA sequence of tgtc_styled_forward_rays on the same operands, so
+ *   rgb[k] and sigma of tgtc_styled_forward_rays_multi are the bits of tgtc_styled_forward_rays(..., z[k], ...), and
+ *   rgb_fine[k], t_fine of tgtc_render_rays_styled_multi are the bits of tgtc_render_rays_styled(..., z[k], ...,
+ *   TGTC_PATH_CHAIN, ...) without coarse outputs; K = 1 is a valid call.
+ * The render is always the chain of per-sample kernels (there is no `path`, tgtc_render_path has no say): the geometry
+ * half of the stylised TGTC_PATH_CHAIN, ONE launch of the multi-latent kernel (csrc/mlp_style_multi.hip), K compositing
+ * launches over the shared sigma / depths.  There are no coarse-image outputs.
+ * Errors: K < 1, R < 0, wrong handle kinds, null pointers, n_coarse < 3, n_fine < 1, NeRF (fine) and style handles of
+ *   different precisions, a workspace below tgtc_render_styled_multi_workspace_bytes -> TGTC_ERR_ARG;
+ *   K x R x N >= 2^31 (N = n_coarse + n_fine for the render) -> TGTC_ERR_UNSUPPORTED: chunk the rays.  R == 0 -> TGTC_OK.
+ * Workspace (device scratch, 0 is returned for negative arguments or K < 1): six planes, each rounded up to 256 bytes, in
+ *   this order:  ts_c, sigma_c, w_c float [R,n_coarse];  ts_f, sigma_f float [R,n_coarse+n_fine];
+ *   rgb_f float [K,R,n_coarse+n_fine,3].  The per-sample colour dominates: a 400 x 400 frame at 128 + 64 and K = 4 takes
+ *   about 1.5 GB (369 MB per latent); chunk the rays where that is too much.
+ * Scratch slab: the kernel keeps base_remap of the tile in a second per-workgroup region (128 KiB per CU, 32 MiB on 256
+ *   CUs) that tgtc_style_create allocates beside the first.  Like the first it belongs to the STYLE HANDLE: two launches
+ *   that use one style handle (these entry points, tgtc_styled_forward_rays, tgtc_render_rays_styled) must not overlap
+ *   on different streams. */
+int tgtc_styled_forward_rays_multi(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o,
+                                   const double* rays_d, const float* ts, const float* z, int K, int64_t R, int N,
+                                   float* rgb, float* sigma, void* stream);
+size_t tgtc_render_styled_multi_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K);
+int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                  const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                  int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                  void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,8 +41,20 @@ EXTRA = {
     "synthetic": (None, False),        # no dataset / checkpoints: seeded weights + closed-form camera path
     "synthetic_hw": (int, 400),        # frame size of the synthetic scene
     "synthetic_frames": (int, 2),      # frames of the synthetic validation path
+    "synthetic_styles": (int, 1),      # styles of the synthetic scene's latent table (1: one style)
+    "share_geometry": (None, False),   # --render_valid_style: all styles of a frame in ONE multi-latent call (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
+}
+
+
+HELP = {
+    "synthetic_styles": "styles of the synthetic scene's latent table (default 1)",
+    "share_geometry": "with --render_valid_style: render all styles of a frame in one multi-latent call that shares the "
+                      "coarse pass, the fine depths and the fine NeRF trunk.  Style 0 is rendered with the jitter it has "
+                      "without the flag (its images agree with such a run to the rounding between the chain and the "
+                      "stylised ray kernel, 1.2e-7 on a pixel); the other styles use style 0's jitter instead of their own "
+                      "draw, so all styles of a frame share sample positions and depth",
 }
 
 
@@ -68,9 +80,9 @@ def config_parser():
     for table in (FLAGS, EXTRA):
         for name, (typ, default) in table.items():
             if typ is None:
-                p.add_argument("--" + name, action="store_true", default=default)
+                p.add_argument("--" + name, action="store_true", default=default, help=HELP.get(name))
             else:
-                p.add_argument("--" + name, type=typ, default=default)
+                p.add_argument("--" + name, type=typ, default=default, help=HELP.get(name))
     return p
 
 

@@ -169,5 +169,6 @@ struct tgtc_net {
     size_t bias2_off, bias2_bytes, stream2_off, stream2_bytes;
     int n_frags2;
     size_t stash_off;  // per-workgroup scratch slabs of the fused stylised kernel
+    size_t stash2_off; // a second region of the same size (base_remap across the latents of mlp_style_multi.hip)
     int n_wg;          // persistent grid size (= CUs)
 };

@@ -479,7 +479,8 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
     net->n_frags2 = ps.n_frags;
     net->n_wg = n_cu;  // one persistent workgroup per CU (the LDS ring allows exactly one)
     net->stash_off = (net->stream2_off + net->stream2_bytes + kChunkBytes + 255) & ~(size_t)255;
-    const size_t total = net->stash_off + (size_t)net->n_wg * kStashBytesPerWG;
+    net->stash2_off = net->stash_off + (size_t)net->n_wg * kStashBytesPerWG;
+    const size_t total = net->stash2_off + (size_t)net->n_wg * kStashBytesPerWG;
     hipError_t e = hipMalloc((void**)&net->dev, total);
     if (e != hipSuccess) {
         delete net;

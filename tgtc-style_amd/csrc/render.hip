@@ -19,6 +19,10 @@ int styled_forward_rays_impl(const tgtc_net* nerf, const tgtc_net* style, const 
                              const float* ts, const float* z, int64_t R, int N, float* rgb, float* sigma,
                              hipStream_t st);
 
+int styled_forward_rays_multi_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                   const float* ts, const float* z, int K, int64_t R, int N, float* rgb, float* sigma,
+                                   hipStream_t st);
+
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RenderWorkspace {
@@ -39,6 +43,28 @@ struct RenderWorkspace {
         ts_f = take((size_t)R * nt);
         sigma_f = take((size_t)R * nt);
         rgb_f = take((size_t)R * nt * 3);
+        total = off;
+    }
+};
+
+// The planes the multi-latent stylised chain uses: RenderWorkspace's without the coarse colours, rgb_f [K,R,Nc+Nf,3].
+struct MultiWorkspace {
+    float *ts_c, *sigma_c, *w_c, *ts_f, *sigma_f, *rgb_f;
+    size_t total;
+    MultiWorkspace(char* base, int64_t R, int nc, int nf, int K) {
+        const int nt = nc + nf;
+        size_t off = 0;
+        auto take = [&](size_t floats) {
+            float* p = reinterpret_cast<float*>(base + off);
+            off += align256(floats * sizeof(float));
+            return p;
+        };
+        ts_c = take((size_t)R * nc);
+        sigma_c = take((size_t)R * nc);
+        w_c = take((size_t)R * nc);
+        ts_f = take((size_t)R * nt);
+        sigma_f = take((size_t)R * nt);
+        rgb_f = take((size_t)K * R * nt * 3);
         total = off;
     }
 };
@@ -175,4 +201,58 @@ extern "C" int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* f
     rc = styled_forward_rays_impl(fine, style, rays_o, rays_d, ws.ts_f, z, R, n_coarse + n_fine, ws.rgb_f, ws.sigma_f, st);
     if (rc) return rc;
     return launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, n_coarse + n_fine, rgb_fine, t_fine, nullptr, st);
+}
+
+extern "C" size_t tgtc_render_styled_multi_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K) {
+    if (R < 0 || n_coarse < 0 || n_fine < 0 || K < 1) return 0;
+    return MultiWorkspace(nullptr, R, n_coarse, n_fine, K).total;
+}
+
+// The stylised render under K latent sets per ray: the geometry half of the stylised chain above (coarse depths -> sigma ->
+// weights -> fine depths) once, ONE launch of styled_rays_multi_kernel (mlp_style_multi.hip: the fine NeRF trunk once per
+// sample, the concat and style MLPs once per sample and latent), then each rgb[k] composited with the shared sigma_f / ts_f.
+extern "C" int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                             const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                             int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                             void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
+                                             void* stream) {
+    TGTC_REQUIRE(coarse && fine && style && R >= 0, "render_rays_styled_multi: bad argument");
+    TGTC_REQUIRE(K >= 1, "render_rays_styled_multi: need K >= 1 latent sets (got %d)", K);
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "render_rays_styled_multi: coarse and fine must be NeRF handles, style a style handle");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    TGTC_REQUIRE(fine->precision == style->precision,
+                 "render_rays_styled_multi: fine NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_multi: null pointer");
+    const int nt = n_coarse + n_fine;
+    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_multi: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    MultiWorkspace ws(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
+    TGTC_REQUIRE(workspace_bytes >= ws.total, "render_rays_styled_multi: workspace of %zu bytes, need %zu", workspace_bytes,
+                 ws.total);
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
+        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
+        rc = launch_fused_depths(coarse->precision, a, st);
+        if (rc) return rc;
+    } else {
+        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
+        if (rc) return rc;
+        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
+        if (rc) return rc;
+        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
+        if (rc) return rc;
+        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+        if (rc) return rc;
+    }
+    rc = styled_forward_rays_multi_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, ws.rgb_f, ws.sigma_f, st);
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) {
+        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, t_fine,
+                              nullptr, st);
+        if (rc) return rc;
+    }
+    return TGTC_OK;
 }

@@ -32,6 +32,7 @@ class RayRenderer:
             raise ValueError("fused must be True, False or 'single'")
         self.coarse, self.fine, self.style, self.fused = coarse, fine, style, fused
         self._ws = None
+        self._ws_multi = None
 
     _REQUEST = {True: hip.PATH_AUTO, "single": hip.PATH_RAY_KERNEL, False: hip.PATH_CHAIN}
 
@@ -98,6 +99,41 @@ class RayRenderer:
         if want_coarse:
             out["rgb_coarse"], out["t_coarse"] = rgb_c, t_c
         return out
+
+    def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None):
+        """The same rays under K latent sets in one call: zs float [K,R,32] -> dict rgb [K,R,3], t [R].
+
+        The coarse pass, the fine depths and the fine NeRF trunk run once and are shared by the K images (one launch of
+        the multi-latent kernel, csrc/mlp_style_multi.hip); rgb[k] and t are the bits of
+        `RayRenderer(..., fused=False).render(..., z=zs[k])`.  Always the chain of per-sample kernels: `fused` has no say.
+        The workspace holds K per-sample colour planes (369 MB per latent for a 400 x 400 frame at 128 + 64)."""
+        hip.require_gpu(rays_o, rays_d, zs)
+        lib = hip.load()
+        if self.style is None or zs is None:
+            raise ValueError("render_latents needs a style pair and zs [K,R,32]")
+        if n_fine <= 0:
+            raise ValueError("N_samples_fine must be > 0 (the reference render paths dereference None otherwise)")
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        R, dev = rays_o.shape[0], rays_o.device
+        zs = zs.to(torch.float32).contiguous()
+        if zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
+            raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
+        K = zs.shape[0]
+        need = lib.tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K)
+        if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
+            self._ws_multi = None       # release the old one first: the two together may not fit
+            self._ws_multi = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        ws = self._ws_multi
+        rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
+        t = torch.empty(R, device=dev, dtype=torch.float32)
+        if jitter is not None:
+            jitter = jitter.to(torch.float32).contiguous()
+        hip.check(lib.tgtc_render_rays_styled_multi(self.coarse.packed().handle, self.fine.packed().handle,
+                                                    self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K,
+                                                    R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), hip.ptr(ws),
+                                                    ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
+        return {"rgb": rgb, "t": t}
 
 
 # =====================================================================================================
@@ -270,17 +306,62 @@ def _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_s
     return rgb_f, t_f
 
 
+def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer):
+    """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
+    `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
+    style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
+    hook (train_tgtcs.SyntheticScene): the rays this rank renders of each frame it takes part in -- its pixel range of
+    every frame under rays sharding, whole frames dealt round-robin under frames sharding."""
+    ds = dataloader.dataset
+    if renderer is None or not hasattr(ds, 'frame_batches'):
+        raise ValueError("share_geometry needs renderer=RayRenderer(...) and a dataset with the frame_batches hook")
+    frame_num, h, w, styles = ds.cps_valid.shape[0], ds.h, ds.w, ds.style_num
+    res = _local_res(ds, h * w)
+    nt = args.N_samples + args.N_samples_fine
+    # rays per call: K x R x nt samples stay below 2^31 and the per-sample colour of a call below 2 GiB
+    per_call = max(1, min(((1 << 31) - 1) // (styles * nt), (2 << 30) // (styles * nt * 12)))
+    rgbs, ts, have = [], [], 0
+    for batch in ds.frame_batches(dataloader.batch_size):
+        b = _to_device(batch, device)
+        fid = int(b['frame_id'][0])
+        R = b['rays_o'].shape[0]
+        for lo in range(0, R, per_call):
+            sl = slice(lo, min(lo + per_call, R))
+            frame_ids = b['frame_id'][sl].long()
+            zs = torch.stack([latents_model_1(style_ids=torch.full_like(frame_ids, sid), frame_ids=frame_ids,
+                                              type=args.dataset_type) for sid in range(styles)])
+            jitter = b['jitter'][sl] if 'jitter' in b else torch.rand(frame_ids.shape[0], args.N_samples, device=device)
+            out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine, near=ds.near,
+                                          far=ds.far, jitter=jitter, zs=zs)
+            rgbs.append(out["rgb"].detach()), ts.append(out["t"].detach())
+        have += R
+        if have == res:           # a frame (this rank's part of it) is complete
+            rgb_all, t_all = torch.cat(rgbs, 1), torch.cat(ts, 0)
+            for sid in range(styles):
+                rgb_img, t_img, writer = _assemble(ds, rgb_all[sid].contiguous(), t_all)
+                if sv_path is not None and writer:
+                    _write_depth_rgb(sv_path, rgb_img, t_img, h, w, 'style_%05d_fine_%05d.png' % (sid, fid),
+                                     'style_%05d_fine_depth_%05d.png' % (sid, fid))
+            rgbs, ts, have = [], [], 0
+    _drain_images()
+    return np.zeros([0, 3], np.float32), np.zeros([0], np.float32)
+
+
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
-                 device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None):
+                 device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
+                 share_geometry=False):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
-    Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference."""
+    Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
+    share_geometry=True (not in the reference): all styles of a frame in one multi-latent call, see _render_style_shared."""
     _require_fine(args)
     latents_model_1.sigma_scale = sigma_scale
     if sv_path is not None:
         os.makedirs(sv_path, exist_ok=True)
     ds = dataloader.dataset
     ds.mode = 'valid_style'
+    if share_geometry:
+        return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0

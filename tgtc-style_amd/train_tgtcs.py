@@ -92,6 +92,25 @@ class SyntheticScene(ShardedScene):
                     batch['jitter'] = jit[lo:lo + n]
                 yield batch
 
+    def frame_batches(self, batch_size):
+        """The validation path by FRAMES, for renders that take all styles of a frame in one call (--share_geometry): the
+        rays this rank renders of each frame -- its pixel range of every frame under rays sharding, whole frames dealt
+        round-robin under frames sharding -- with the jitter of the frame's style-0 image (image index 0 * frames + fid)."""
+        poses = self.cps_valid
+        first, last = self._pixels()
+        for fid in range(len(poses)):
+            if self.shard != 'rays' and fid % self.world != self.rank:
+                continue
+            o, d = utils.gen_rays(self.h, self.w, self.f, poses[fid][:3, :4], first_pixel=first, n=last - first,
+                                  device=self.device)
+            jit = self.image_jitter(fid)[first:last] if self.jitter_samples else None
+            for lo in range(0, last - first, batch_size):
+                n = min(batch_size, last - first - lo)
+                batch = {'rays_o': o[lo:lo + n], 'rays_d': d[lo:lo + n], 'frame_id': torch.full((n,), fid, dtype=torch.long)}
+                if jit is not None:
+                    batch['jitter'] = jit[lo:lo + n]
+                yield batch
+
 
 class LlffPoseScene(SyntheticScene):
     """A real LLFF scene as far as rendering needs it: camera poses from `<datadir>/poses_bounds.npy`
@@ -194,7 +213,8 @@ def train(args):
                                 style_num=stylized["style_num"] if stylized else 1)
     elif args.synthetic:
         hw = args.synthetic_hw
-        dataset = SyntheticScene(hw, hw, frames=20, valid_frames=args.synthetic_frames, device=device)
+        dataset = SyntheticScene(hw, hw, frames=20, valid_frames=args.synthetic_frames, device=device,
+                                 style_num=args.synthetic_styles)
     else:
         raise SystemExit("train_tgtcs: no poses_bounds.npy in --datadir %s (the image side of the LLFF loader is not part "
                          "of this build, SURVEY section 8f); run with --synthetic for the seeded scene" % args.datadir)
@@ -249,7 +269,8 @@ def train(args):
             out = os.path.join(sv_path, 'render_valid_' + str(global_step))
             model.set_enable_style(True), model_fine.set_enable_style(True)
             dataset.mode = 'valid_style'
-            rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, **common, **styled)
+            rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, share_geometry=args.share_geometry,
+                                   **common, **styled)
             print('Done, saving to', out)
             return out
         if args.render_train_style:
