@@ -233,6 +233,40 @@ int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_net* fine, 
                                   int n_coarse, int n_fine, float near_, float far_, const float* jitter,
                                   void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
 
+/* ------------------------------------------------------------------ K latent sets per ray, style networks on live samples only
+ * tgtc_render_rays_styled_multi with the per-latent work culled.  In the stylised chain sigma depends on the ray alone, so
+ * the compositing weight w_i = alpha_i x T_i of every fine sample is known before a style network has run; a sample with
+ * w_i == 0 (relu(sigma_i) = 0) enters rgb = sum w_i x c_i as exactly +0 whatever finite colour the style MLP would give.
+ * Order of work on the stream: the geometry half of the multi render; a sigma-only pass of the fine NeRF over all R x N
+ * samples (N = n_coarse + n_fine); tgtc_composite's kernel for t_fine and the weights plane w_f; a compaction that writes
+ * the ASCENDING list live[] of the sample indices s = r x N + i with w_f[s] > min_weight and its length, both on the
+ * device; hipMemsetAsync of the K colour planes; ONE launch of the indexed multi-latent kernel (csrc/mlp_style_sparse.hip:
+ * NeRF trunk + concat MLP + style MLP over the list, the number of tiles read from the device count, rgb scattered to the
+ * dense planes); K compositing launches over the shared sigma / depths.  The host never learns the count.
+ * min_weight = 0: rgb_fine[k], t_fine are the BITS of tgtc_render_rays_styled_multi (a live sample's result does not depend
+ *   on which samples share its tile; a dead sample contributes +0 either way).
+ * min_weight > 0: t_fine is unchanged (depth never sees the colours); colours lie in [0,1], so each ray and channel moves
+ *   by at most the sum of the ray's dropped weights (those with 0 < w <= min_weight), up to float32 summation rounding.
+ * Cost per fine sample with live fraction f: 491 264 + f x (556 800 + K x 950 112) multiply-accumulates against
+ *   556 800 + K x 950 112 of the multi render; break-even at K = 1 is f ~ 0.67, and with everything live the call costs
+ *   1.33 x the multi render.  It is a mode the caller asks for; no `path` rule ever selects it.
+ * Layouts, conventions and errors are those of tgtc_render_rays_styled_multi; additionally min_weight < 0 or NaN ->
+ *   TGTC_ERR_ARG.  Every argument check returns before a device is touched.
+ * live_count: device pointer to ONE uint32 that receives the length of the list, or NULL.
+ * Workspace (0 is returned for negative arguments or K < 1), each plane rounded up to 256 bytes, in this order:
+ *   the six planes of tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K);
+ *   w_f   float  [R,N]   the fine compositing weights (the bits of tgtc_composite's weights output on sigma_f, ts_f);
+ *   live  uint32 [R x N] the list (the first `count` entries are written);
+ *   8192 bytes of scratch for the compaction: word 0 is the count, the rest partial counts.
+ * Scratch slab: as for the multi render, both slab regions of the STYLE HANDLE are used; launches on one style handle
+ *   must not overlap. */
+size_t tgtc_render_styled_sparse_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K);
+int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                   const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                   int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                   float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                   float* t_fine, uint32_t* live_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXTRA = {
     "synthetic_frames": (int, 2),      # frames of the synthetic validation path
     "synthetic_styles": (int, 1),      # styles of the synthetic scene's latent table (1: one style)
     "share_geometry": (None, False),   # --render_valid_style: all styles of a frame in ONE multi-latent call (HELP below)
+    "cull_weight": (float, -1.0),      # stylised renders: style networks only where the compositing weight exceeds it (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
 }
@@ -55,6 +56,11 @@ HELP = {
                       "without the flag (its images agree with such a run to the rounding between the chain and the "
                       "stylised ray kernel, 1.2e-7 on a pixel); the other styles use style 0's jitter instead of their own "
                       "draw, so all styles of a frame share sample positions and depth",
+    "cull_weight": "with --render_valid_style (with or without --share_geometry) or --render_train_style: run the style "
+                   "networks only on the fine samples whose compositing weight exceeds this value, after a sigma-only pass "
+                   "over all samples.  0 reproduces the image of the chain of per-sample kernels bit for bit (samples of "
+                   "weight exactly 0 add +0 to a pixel); a positive value bounds the change of each ray by the sum of its "
+                   "dropped weights and leaves the depth image alone.  Default -1: off, every sample is styled",
 }
 
 

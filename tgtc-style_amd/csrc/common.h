@@ -42,4 +42,8 @@ int cu_count(int& cus);
 
 constexpr int kWave = 64;
 
+// Fixed scratch at the end of the culled stylised render's workspace (include/tgtc_hip.h, tgtc_render_styled_sparse_workspace_bytes):
+// word 0 the live count, then the partial counts of the compaction (mlp_style_sparse.hip); render.hip lays it out.
+constexpr size_t kSparseScratchBytes = 8192;
+
 }  // namespace tgtc

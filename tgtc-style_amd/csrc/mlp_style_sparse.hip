@@ -1,0 +1,388 @@
+// Stylised path over a compact list of samples: the style networks only where the compositing weight can matter.
+//
+// In the stylised chain sigma depends on the ray alone, so the compositing weight w = alpha * T of every fine sample is
+// known before any style network has run (tgtc_render_rays_styled_sparse, render.hip: sigma pass -> tgtc_composite weights).
+// A sample with w == 0 enters rgb = sum w * c as exactly +0 whatever finite colour the style MLP would give it.
+//
+//   compact_count_kernel / compact_write_kernel   live[] = ascending sample indices s = r * N + i with w[s] > min_weight,
+//                                                 n_live, both on the device; deterministic (no atomics): kCompactParts
+//                                                 contiguous ranges are counted, then each range writes behind the sum of
+//                                                 the counts in front of it, lanes in order through ballots.
+//   styled_rays_sparse_kernel                     styled_rays_multi_kernel (mlp_style_multi.hip) with its samples gathered
+//                                                 through the list: tile t owns live[t * SAMPLES_PER_WG ...], past the end
+//                                                 clamped to the last live sample; r, ts[s], z[k,r] follow from the sample
+//                                                 index as there; rgb[k,s] is scattered to its dense position (the caller
+//                                                 zero-fills the planes); sigma is not written.  The number of tiles comes
+//                                                 from n_live read on the device.
+//
+// Per latent this is the MFMA sequence of styled_rays_multi_kernel on the same operands, and a column (sample) of an MFMA
+// does not depend on the other columns of its tile, so a live sample carries the bits of the dense kernels.
+#include "mlp_core.h"
+#include "mlp_layouts.h"
+#include "mlp_pack.h"
+#include "mlp_style_chain.h"
+
+namespace tgtc {
+
+struct StyledSparseArgs {
+    const char* nerf_bias;
+    const char* nerf_stream;
+    const char* pair_bias;
+    const char* concat_stream;
+    const char* style_stream;
+    char* stash;             // region A: gridDim.x * kStashBytesPerWG
+    long long stash2_delta;  // region B of a workgroup lies this many bytes behind its region A
+    long long M;             // R * N samples (per latent)
+    long long R;
+    int N;
+    int K;
+    const double* rays_o;
+    const double* rays_d;
+    const float* ts;
+    const float* z;            // [K,R,32]
+    const unsigned* live;      // [n_live] ascending sample indices
+    const unsigned* n_live;    // device scalar
+    float* rgb;                // [K,R,N,3], zero-filled by the caller
+};
+
+// concat | style, both chunk aligned (as PairMap of mlp_style_multi.hip)
+template <class C>
+struct SparsePairMap {
+    static constexpr int F_CONCAT = 0;
+    static constexpr int F_STYLE = kConcatFrags;
+    static constexpr int NFRAG = F_STYLE + kStyleFrags;
+    static constexpr int NSEG = 2;
+    static constexpr int chunk0(int i) { return i == 0 ? 0 : i == 1 ? F_STYLE / C::FPC : (1 << 30); }
+    static_assert(kConcatFrags % C::FPC == 0, "concat stream must end on a chunk boundary");
+};
+
+template <class C>
+__global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_sparse_kernel(StyledSparseArgs a) {
+    constexpr int NCT = C::NCT;
+    constexpr bool SPLIT = C::SPLIT;
+    using Map = SparsePairMap<C>;
+    using L = NerfLayout;
+    __shared__ __attribute__((aligned(16))) char smem[kRingBytes + kNerfBiasBytes + kStylePairBiasBytes];
+
+    // the list's length decides the tiles; a workgroup without one leaves before any LDS-DMA is issued (none may be in
+    // flight when it ends), which is also what keeps live[n_live - 1] from being read when nothing is live
+    const unsigned n_live = *a.n_live;
+    const unsigned n_tiles = (n_live + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;   // n_live < 2^31
+    if (blockIdx.x >= n_tiles) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, n = lane & 15;
+    char* slab = a.stash + (size_t)blockIdx.x * kStashBytesPerWG + (size_t)tid * 16;    // this lane's 16-byte column, region A
+
+    WeightStream<C, SingleStreamMap<kTrunkFrags>> wt;
+    WeightStream<C, Map> ws;
+    const char* const trunk_streams[1] = {a.nerf_stream};
+    wt.init(trunk_streams, smem, wave, lane);
+    ws.src[0] = ws.lane_src(a.concat_stream, wave, lane);
+    ws.src[1] = ws.lane_src(a.style_stream, wave, lane);
+    ws.voff = wt.voff, ws.lds_wave = wt.lds_wave, ws.lane_lo = wt.lane_lo, ws.lane_hi = wt.lane_hi;
+    // bias tables: loaded once per workgroup (LDS-DMA), visible after the first ring barrier
+#pragma unroll
+    for (int j = 0; j < kNerfBiasBytes / (C::NWAVES * 1024); ++j)
+        __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.nerf_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
+                                         TGTC_LPTR(smem + kRingBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
+        __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.pair_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
+                                         TGTC_LPTR(smem + kRingBytes + kNerfBiasBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+    const lds_cptr nerf_bias = opaque((lds_cptr)smem + kRingBytes + 16 * g);
+    const lds_cptr pair_bias = opaque((lds_cptr)smem + kRingBytes + kNerfBiasBytes + 16 * g);
+
+    for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        // ---- inputs, gathered through the list
+        const unsigned i_wave = tile * C::SAMPLES_PER_WG + wave * C::SAMPLES_PER_WAVE;
+        double pos[NCT][3];
+        unsigned sidx[NCT];     // dense sample index (< M < 2^31) of the column, clamped to the last live sample
+        unsigned own = 0;       // bit c: column c is a live sample of this tile (not a clamped copy)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) {
+            unsigned i = i_wave + c * 16 + n;
+            if (i < n_live) own |= 1u << c;
+            else i = n_live - 1;
+            const unsigned s = a.live[i];
+            sidx[c] = s;
+            const long long r = s / (unsigned)a.N;
+            const double t = (double)a.ts[s];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pos[c][k] = a.rays_o[r * 3 + k] + t * a.rays_d[r * 3 + k];
+            // retire the loads before any LDS-DMA is issued (their wait would drain the whole prefetch)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(pos[c][k]));
+        }
+        // previous tile: every wave must be done with the ring before it is refilled
+        __builtin_amdgcn_s_barrier();
+        wt.prologue();
+
+        half8 pe_h[2][NCT], pe_l[2][NCT];
+        // (an opaque copy keeps the encoder's selectors inside the tile, as in styled_rays_multi_kernel)
+        int g_enc = g;
+        asm volatile("" : "+v"(g_enc));
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) {
+            half8 h2[2], l2[2];
+            encode_point<SPLIT, SPLIT>(pos[c], g_enc, h2, l2, nullptr);
+            pe_h[0][c] = h2[0], pe_h[1][c] = h2[1], pe_l[0][c] = l2[0], pe_l[1][c] = l2[1];
+        }
+        wt.start();
+
+        half8 Xh[8][NCT], Xl[8][NCT], Yh[8][NCT], Yl[8][NCT];
+        auto to_Y = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+            constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+            store_act<C, rt, decltype(h_)::value>(acc, Yh[rt / 2][c], Yl[rt / 2][c]);
+        };
+        auto to_X = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+            constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+            store_act<C, rt, decltype(h_)::value>(acc, Xh[rt / 2][c], Xl[rt / 2][c]);
+        };
+        // ---- NeRF trunk (models.py:95-101), once per tile
+        dense_layer<C, L::frag0(0), 2, 16, L::bias0(0)>(wt, nerf_bias, pe_h, pe_l, to_Y);
+        dense_layer<C, L::frag0(1), 8, 16, L::bias0(1)>(wt, nerf_bias, Yh, Yl, to_X);
+        dense_layer<C, L::frag0(2), 8, 16, L::bias0(2)>(wt, nerf_bias, Xh, Xl, to_Y);
+        dense_layer<C, L::frag0(3), 8, 16, L::bias0(3)>(wt, nerf_bias, Yh, Yl, to_X);
+        dense_layer<C, L::frag0(4), 8, 16, L::bias0(4)>(wt, nerf_bias, Xh, Xl, to_Y);
+        {
+            half8 Bh[10][NCT], Bl[10][NCT];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) append<C>(Bh, Bl, k, Yh[k], Yl[k]);
+            append<C>(Bh, Bl, 8, pe_h[0], pe_l[0]);
+            append<C>(Bh, Bl, 9, pe_h[1], pe_l[1]);
+            dense_layer<C, L::frag0(5), 10, 16, L::bias0(5)>(wt, nerf_bias, Bh, Bl, to_X);
+        }
+        dense_layer<C, L::frag0(6), 8, 16, L::bias0(6)>(wt, nerf_bias, Xh, Xl, to_Y);
+        dense_layer<C, L::frag0(7), 8, 16, L::bias0(7)>(wt, nerf_bias, Yh, Yl, to_X);
+        // sigma_layer: its fragments lie in the stream between layer 7's and base_remap's, so the layer is walked as in
+        // styled_rays_multi_kernel (same windows, same ring timing); sigma came from the sigma pass and is not written again
+        dense_layer<C, L::frag0(8), 8, 1, L::bias0(8)>(wt, nerf_bias, Xh, Xl, [&](auto, auto, auto h_, const float4v& acc) {
+            if constexpr (decltype(h_)::value == 0) asm volatile("" ::"v"(acc[0]));
+        });
+        // base_remap: streams to slab region B as it is produced, where it stays for the K iterations
+        {
+            half8 Th[NCT], Tl[NCT];
+            dense_layer<C, L::frag0(9), 8, 16, L::bias0(9)>(wt, nerf_bias, Xh, Xl, [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+                constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value, hf = decltype(h_)::value;
+                store_act<C, rt, hf>(acc, Th[c], Tl[c]);
+                if constexpr ((rt & 1) && hf == 1) stash_store<C>(slab + a.stash2_delta, rt / 2, c, Th[c], Tl[c]);
+            });
+        }
+
+        for (int k = 0; k < a.K; ++k) {
+            // ---- latent k of the tile's rays
+            float zsum[NCT];
+            half8 z_h[NCT], z_l[NCT], zb_h[NCT], zb_l[NCT];
+#pragma unroll
+            for (int c = 0; c < NCT; ++c) {
+                const long long r = sidx[c] / (unsigned)a.N;
+                const float* zr = a.z + ((long long)k * a.R + r) * 32;
+                float part = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) part += zr[8 * g + j];
+                load_vec32<SPLIT>(zr, g, z_h[c], z_l[c]);
+                zsum[c] = part;
+                // retired before the ring is restarted, as the tile's inputs are
+                asm volatile("" : "+v"(zsum[c]), "+v"(z_h[c]));
+                if constexpr (SPLIT) asm volatile("" : "+v"(z_l[c]));
+            }
+            // every wave must be done with the previous stream before the ring is refilled
+            __builtin_amdgcn_s_barrier();
+            ws.prologue();
+#pragma unroll
+            for (int c = 0; c < NCT; ++c) {
+                // rendering.py:126: mean over the 32 latent channels, broadcast back to 32 (rendering.py:139)
+                float zs = zsum[c];
+                zs += __shfl_xor(zs, 16);
+                zs += __shfl_xor(zs, 32);
+                splat8<SPLIT>(zs * (1.0f / 32.0f), zb_h[c], zb_l[c]);
+            }
+            ws.start();
+
+            // ---- concat MLP -> Y
+            concat_mlp<C, Map::F_CONCAT, 0>(ws, pair_bias, pe_h, pe_l, z_h, z_l, Xh, Xl, Yh, Yl);
+            // ---- style layer 0 on [remap (slab B -> X) | concat_features (Y) | pe | mean z]; outputs stream to slab A
+            stash_load<C>(slab + a.stash2_delta, Xh, Xl);
+            {
+                half8 Bh[19][NCT], Bl[19][NCT];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) append<C>(Bh, Bl, i, Xh[i], Xl[i]);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) append<C>(Bh, Bl, 8 + i, Yh[i], Yl[i]);
+                append<C>(Bh, Bl, 16, pe_h[0], pe_l[0]);
+                append<C>(Bh, Bl, 17, pe_h[1], pe_l[1]);
+                append<C>(Bh, Bl, 18, zb_h, zb_l);
+                half8 Th[NCT], Tl[NCT];
+                dense_layer<C, Map::F_STYLE + style_frag0(0), 19, 16, kConcatBiasFloats + style_bias0(0)>(
+                    ws, pair_bias, Bh, Bl, [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+                        constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value, hf = decltype(h_)::value;
+                        store_act<C, rt, hf>(acc, Th[c], Tl[c]);
+                        if constexpr ((rt & 1) && hf == 1) stash_store<C>(slab, rt / 2, c, Th[c], Tl[c]);
+                    });
+            }
+            stash_load<C>(slab, Xh, Xl);
+            // ---- style layers 1..7 -> rgb[k], scattered to the sample's dense position (models.py:172-179)
+            float* rgb_k = a.rgb + (long long)k * a.M * 3;
+            style_tail<C, Map::F_STYLE, kConcatBiasFloats>(ws, pair_bias, pe_h, pe_l, zb_h, zb_l, Xh, Xl, Yh, Yl,
+                                                           [&](auto c_, auto h_, const float4v& acc) {
+                                                               constexpr int c = decltype(c_)::value, hf = decltype(h_)::value;
+                                                               if (g == 0 && (own >> c & 1)) {
+#pragma unroll
+                                                                   for (int r = 2 * hf; r < (hf ? 3 : 2); ++r)
+                                                                       rgb_k[(size_t)sidx[c] * 3 + r] = 1.0f / (1.0f + expf(-acc[r]));
+                                                               }
+                                                           });
+        }
+    }
+}
+
+using CfgFast = MlpCfg<8, 2, false, 4>;  // the geometries of styled_rays_multi_kernel
+using CfgExact = MlpCfg<8, 1, true, 4>;
+
+// The fp16 instance is compiled in a translation unit of its own (this source with -DTGTC_TU_FP16_ONLY) so that the two
+// kernels build in parallel.
+template <class C>
+void launch_styled_rays_sparse(unsigned grid, const StyledSparseArgs& a, hipStream_t st) {
+    styled_rays_sparse_kernel<C><<<grid, C::NWAVES * 64, 0, st>>>(a);
+}
+#ifdef TGTC_TU_FP16_ONLY
+template void launch_styled_rays_sparse<CfgFast>(unsigned, const StyledSparseArgs&, hipStream_t);
+}  // namespace tgtc
+#else
+extern template void launch_styled_rays_sparse<CfgFast>(unsigned, const StyledSparseArgs&, hipStream_t);
+
+// ------------------------------------------------------------------------------------------------ compaction
+// The plane of M weights is cut into kCompactParts contiguous ranges of `span` samples (a multiple of the block size).
+// Pass 1 counts the live samples of each range; pass 2 sums the counts in front of its range and writes the range's live
+// indices behind them, 256 samples per step in lane order.  scratch: word 0 = n_live, words 64 .. 64 + kCompactParts the
+// counts (every word is written by every call: nothing to initialise).
+constexpr int kCompactParts = 1024;
+constexpr int kCompactBlock = 256;
+constexpr int kCompactCountWord = 64;
+
+__device__ __forceinline__ bool is_live(float w, float min_weight) { return w > min_weight; }   // false for NaN
+
+__global__ void __launch_bounds__(kCompactBlock) compact_count_kernel(const float* __restrict__ w, unsigned M, unsigned span,
+                                                                      float min_weight, unsigned* __restrict__ scratch) {
+    __shared__ unsigned wave_n[kCompactBlock / 64];
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * span;
+    const unsigned lo = b0 < M ? (unsigned)b0 : M;
+    const unsigned hi = b0 + span < M ? (unsigned)(b0 + span) : M;
+    unsigned cnt = 0;
+    for (unsigned s = lo + threadIdx.x; s < hi; s += kCompactBlock) cnt += is_live(w[s], min_weight) ? 1u : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned tot = 0;
+#pragma unroll
+        for (int i = 0; i < kCompactBlock / 64; ++i) tot += wave_n[i];
+        scratch[kCompactCountWord + blockIdx.x] = tot;
+    }
+}
+
+__global__ void __launch_bounds__(kCompactBlock) compact_write_kernel(const float* __restrict__ w, unsigned M, unsigned span,
+                                                                      float min_weight, const unsigned* __restrict__ counts,
+                                                                      unsigned* __restrict__ live, unsigned* __restrict__ n_live,
+                                                                      unsigned* __restrict__ live_count) {
+    __shared__ unsigned red[kCompactBlock / 64];
+    __shared__ unsigned wave_n[2][kCompactBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // samples live in the ranges in front of this one (and, for the last block, the total)
+    unsigned before = 0, all = 0;
+    for (unsigned p = threadIdx.x; p < kCompactParts; p += kCompactBlock) {
+        const unsigned c = counts[p];
+        all += c;
+        if (p < blockIdx.x) before += c;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d), all += __shfl_xor(all, d);
+    if (lane == 0) red[wave] = before;
+    __syncthreads();
+    unsigned base = 0;
+#pragma unroll
+    for (int i = 0; i < kCompactBlock / 64; ++i) base += red[i];
+    if (blockIdx.x == kCompactParts - 1) {
+        __syncthreads();
+        if (lane == 0) red[wave] = all;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned tot = 0;
+#pragma unroll
+            for (int i = 0; i < kCompactBlock / 64; ++i) tot += red[i];
+            *n_live = tot;
+            if (live_count) *live_count = tot;
+        }
+    }
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * span;
+    const unsigned lo = b0 < M ? (unsigned)b0 : M;
+    const unsigned hi = b0 + span < M ? (unsigned)(b0 + span) : M;
+    // whole steps for every thread (the barrier inside is reached by all)
+    int it = 0;
+    for (unsigned s0 = lo; s0 < hi; s0 += kCompactBlock, ++it) {
+        const unsigned s = s0 + threadIdx.x;
+        const bool keep = s < hi && is_live(w[s], min_weight);
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_n[it & 1][wave] = (unsigned)__popcll(m);
+        __syncthreads();   // the buffer written two steps ago is free: every wave has passed the barrier in between
+        unsigned at = base, step = 0;
+#pragma unroll
+        for (int i = 0; i < kCompactBlock / 64; ++i) {
+            const unsigned c = wave_n[it & 1][i];
+            if (i < wave) at += c;
+            step += c;
+        }
+        if (keep) live[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = s;   // at + rank < n_live <= M
+        base += step;
+    }
+}
+
+int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
+                        hipStream_t st) {
+    // span: a multiple of the block size with kCompactParts * span >= M
+    const int64_t per = (M + kCompactParts - 1) / kCompactParts;
+    const unsigned span = (unsigned)((per + kCompactBlock - 1) / kCompactBlock * kCompactBlock);
+    compact_count_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch);
+    TGTC_LAUNCH_CHECK();
+    compact_write_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch + kCompactCountWord,
+                                                                  live, scratch, live_count);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+static_assert((kCompactCountWord + kCompactParts) * sizeof(uint32_t) <= kSparseScratchBytes, "counts must fit the scratch");
+
+// rgb[k, s] for the samples of the list; the caller has zero-filled rgb.  n_live is read on the device: the grid is sized
+// for the dense plane and workgroups without a tile leave at once.
+int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const float* ts, const float* z, int K, int64_t R, int N, const uint32_t* live,
+                                    const uint32_t* n_live, float* rgb, hipStream_t st) {
+    if (nerf->precision != style->precision)
+        return fail(TGTC_ERR_ARG, "styled_forward_rays_sparse: NeRF and style nets were packed with different precisions");
+    constexpr int64_t kLimit = (int64_t)1 << 31;
+    if (R >= kLimit || R * (int64_t)N >= kLimit || R * (int64_t)N * K >= kLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "styled_forward_rays_sparse: K x R x N >= 2^31 in one launch (chunk the rays)");
+    StyledSparseArgs a{};
+    a.nerf_bias = nerf->dev, a.nerf_stream = nerf->dev + nerf->bias_bytes;
+    a.pair_bias = style->dev, a.concat_stream = style->dev + style->bias_bytes;
+    a.style_stream = style->dev + style->stream2_off;
+    a.stash = style->dev + style->stash_off, a.stash2_delta = (long long)(style->stash2_off - style->stash_off);
+    a.M = R * (int64_t)N, a.R = R, a.N = N, a.K = K;
+    a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.z = z, a.live = live, a.n_live = n_live, a.rgb = rgb;
+    if (nerf->precision == TGTC_PREC_FP16) {
+        const long long tiles = (a.M + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgFast>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    } else {
+        const long long tiles = (a.M + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgExact>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    }
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+}  // namespace tgtc
+#endif  // TGTC_TU_FP16_ONLY

@@ -23,6 +23,12 @@ int styled_forward_rays_multi_impl(const tgtc_net* nerf, const tgtc_net* style, 
                                    const float* ts, const float* z, int K, int64_t R, int N, float* rgb, float* sigma,
                                    hipStream_t st);
 
+int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const float* ts, const float* z, int K, int64_t R, int N, const uint32_t* live,
+                                    const uint32_t* n_live, float* rgb, hipStream_t st);
+int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
+                        hipStream_t st);
+
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RenderWorkspace {
@@ -66,6 +72,22 @@ struct MultiWorkspace {
         sigma_f = take((size_t)R * nt);
         rgb_f = take((size_t)K * R * nt * 3);
         total = off;
+    }
+};
+
+// The culled stylised chain: MultiWorkspace's six planes, then the fine weights w_f [R,Nc+Nf], the list live [R*(Nc+Nf)]
+// and the fixed scratch of the compaction (word 0: the live count; mlp_style_sparse.hip).
+struct SparseWorkspace {
+    MultiWorkspace m;
+    float* w_f;
+    uint32_t *live, *scratch;
+    size_t total;
+    SparseWorkspace(char* base, int64_t R, int nc, int nf, int K) : m(base, R, nc, nf, K) {
+        const size_t plane = align256((size_t)R * (nc + nf) * sizeof(float));
+        w_f = reinterpret_cast<float*>(base + m.total);
+        live = reinterpret_cast<uint32_t*>(base + m.total + plane);
+        scratch = reinterpret_cast<uint32_t*>(base + m.total + 2 * plane);
+        total = m.total + 2 * plane + kSparseScratchBytes;
     }
 };
 }  // namespace tgtc
@@ -251,6 +273,78 @@ extern "C" int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_
     if (rc) return rc;
     for (int k = 0; k < K; ++k) {
         rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, t_fine,
+                              nullptr, st);
+        if (rc) return rc;
+    }
+    return TGTC_OK;
+}
+
+extern "C" size_t tgtc_render_styled_sparse_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K) {
+    if (R < 0 || n_coarse < 0 || n_fine < 0 || K < 1) return 0;
+    return SparseWorkspace(nullptr, R, n_coarse, n_fine, K).total;
+}
+
+// The multi-latent stylised render with the style networks only on the samples whose compositing weight exceeds
+// min_weight: geometry half as above, a sigma-only pass of the fine NeRF over every sample, the existing compositing kernel
+// for depth + weights, the compaction, then the indexed multi-latent kernel (mlp_style_sparse.hip) into zero-filled colour
+// planes and K compositing launches over the shared sigma / depths.
+extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                              const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                              int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                              float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                              float* t_fine, uint32_t* live_count, void* stream) {
+    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse: need K >= 1 latent sets (got %d)", K);
+    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse: min_weight must be >= 0 and not NaN (got %g)", (double)min_weight);
+    TGTC_REQUIRE(coarse && fine && style && R >= 0, "render_rays_styled_sparse: bad argument");
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "render_rays_styled_sparse: coarse and fine must be NeRF handles, style a style handle");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    TGTC_REQUIRE(fine->precision == style->precision,
+                 "render_rays_styled_sparse: fine NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse: null pointer");
+    const int nt = n_coarse + n_fine;
+    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
+    TGTC_REQUIRE(workspace_bytes >= sw.total, "render_rays_styled_sparse: workspace of %zu bytes, need %zu", workspace_bytes,
+                 sw.total);
+    const MultiWorkspace& ws = sw.m;
+    hipStream_t st = as_stream(stream);
+    int rc;
+    // 1. geometry half, as tgtc_render_rays_styled_multi
+    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
+        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
+        rc = launch_fused_depths(coarse->precision, a, st);
+        if (rc) return rc;
+    } else {
+        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
+        if (rc) return rc;
+        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
+        if (rc) return rc;
+        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
+        if (rc) return rc;
+        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+        if (rc) return rc;
+    }
+    // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
+    //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
+    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
+    if (rc) return rc;
+    // 3. depth image and the weights plane
+    rc = launch_composite(nullptr, ws.sigma_f, ws.ts_f, R, nt, nullptr, t_fine, sw.w_f, st);
+    if (rc) return rc;
+    // 4. the ascending list of samples with w > min_weight
+    rc = launch_compact_live(sw.w_f, R * (int64_t)nt, min_weight, sw.live, sw.scratch, live_count, st);
+    if (rc) return rc;
+    // 5. dead samples keep colour +0
+    TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
+    // 6. trunk + concat MLP + style MLP over the list
+    rc = styled_forward_rays_sparse_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    if (rc) return rc;
+    // 7. compositing over the shared sigma / depths
+    for (int k = 0; k < K; ++k) {
+        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, nullptr,
                               nullptr, st);
         if (rc) return rc;
     }

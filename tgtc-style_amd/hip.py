@@ -63,7 +63,8 @@ _SIGNATURES = {
     "tgtc_latents_backward": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p],
 }
 _RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_render_workspace_bytes": c_size_t,
-             "tgtc_render_styled_multi_workspace_bytes": c_size_t}
+             "tgtc_render_styled_multi_workspace_bytes": c_size_t,
+             "tgtc_render_styled_sparse_workspace_bytes": c_size_t}
 _OPTIONAL = {
     "tgtc_style_create": [ctypes.POINTER(Linear), c_int, ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],
     "tgtc_concat_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
@@ -78,6 +79,10 @@ _OPTIONAL = {
     "tgtc_render_styled_multi_workspace_bytes": [c_int64, c_int, c_int, c_int],
     "tgtc_render_rays_styled_multi": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                       c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_render_styled_sparse_workspace_bytes": [c_int64, c_int, c_int, c_int],
+    "tgtc_render_rays_styled_sparse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                       c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p,
+                                       c_void_p, c_void_p],
 }
 
 

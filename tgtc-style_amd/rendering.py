@@ -62,8 +62,21 @@ class RayRenderer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
-    def render(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, z=None, want_coarse=False):
-        """rays_o, rays_d float64 [R,3] on the GPU -> dict rgb [R,3], t [R] (+ rgb_coarse, t_coarse)."""
+    def render(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, z=None, want_coarse=False,
+               min_weight=None):
+        """rays_o, rays_d float64 [R,3] on the GPU -> dict rgb [R,3], t [R] (+ rgb_coarse, t_coarse).
+
+        min_weight (stylised render only, a float >= 0): the style networks run only on the fine samples whose compositing
+        weight exceeds it -- `render_latents(..., min_weight=...)` with K = 1, returning rgb [R,3], t [R] and "live"."""
+        if min_weight is not None:
+            if want_coarse:
+                raise ValueError("min_weight and want_coarse exclude each other (the culled render has no coarse image)")
+            if self.style is None or z is None:
+                raise ValueError("min_weight belongs to the stylised render: it needs a style pair and z")
+            out = self.render_latents(rays_o, rays_d, n_coarse, n_fine, near=near, far=far, jitter=jitter,
+                                      zs=z.unsqueeze(0), min_weight=min_weight)
+            out["rgb"] = out["rgb"][0]
+            return out
         hip.require_gpu(rays_o, rays_d)
         lib = hip.load()
         if n_fine <= 0:
@@ -100,13 +113,19 @@ class RayRenderer:
             out["rgb_coarse"], out["t_coarse"] = rgb_c, t_c
         return out
 
-    def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None):
+    def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None, min_weight=None):
         """The same rays under K latent sets in one call: zs float [K,R,32] -> dict rgb [K,R,3], t [R].
 
         The coarse pass, the fine depths and the fine NeRF trunk run once and are shared by the K images (one launch of
         the multi-latent kernel, csrc/mlp_style_multi.hip); rgb[k] and t are the bits of
         `RayRenderer(..., fused=False).render(..., z=zs[k])`.  Always the chain of per-sample kernels: `fused` has no say.
-        The workspace holds K per-sample colour planes (369 MB per latent for a 400 x 400 frame at 128 + 64)."""
+        The workspace holds K per-sample colour planes (369 MB per latent for a 400 x 400 frame at 128 + 64).
+
+        min_weight=None is that call.  A float >= 0 takes tgtc_render_rays_styled_sparse instead: sigma of every fine sample
+        first, then the NeRF trunk and the style networks only on the samples whose compositing weight exceeds min_weight
+        (csrc/mlp_style_sparse.hip).  0 reproduces the images bit for bit; a positive value changes each ray by at most the
+        sum of its dropped weights and leaves t alone.  The result then carries "live": the number of samples the style
+        networks ran on, a device scalar (int32 view of the library's uint32) that is NOT synchronised."""
         hip.require_gpu(rays_o, rays_d, zs)
         lib = hip.load()
         if self.style is None or zs is None:
@@ -120,7 +139,13 @@ class RayRenderer:
         if zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
             raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
         K = zs.shape[0]
-        need = lib.tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K)
+        if min_weight is not None:
+            min_weight = float(min_weight)
+            if not min_weight >= 0:
+                raise ValueError("min_weight must be >= 0 (got %r)" % min_weight)
+            need = lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, K)
+        else:
+            need = lib.tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K)
         if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
             self._ws_multi = None       # release the old one first: the two together may not fit
             self._ws_multi = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
@@ -129,6 +154,14 @@ class RayRenderer:
         t = torch.empty(R, device=dev, dtype=torch.float32)
         if jitter is not None:
             jitter = jitter.to(torch.float32).contiguous()
+        if min_weight is not None:
+            live = torch.zeros((), device=dev, dtype=torch.int32)
+            hip.check(lib.tgtc_render_rays_styled_sparse(self.coarse.packed().handle, self.fine.packed().handle,
+                                                         self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs),
+                                                         K, R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
+                                                         min_weight, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t),
+                                                         hip.ptr(live), hip.stream()))
+            return {"rgb": rgb, "t": t, "live": live}
         hip.check(lib.tgtc_render_rays_styled_multi(self.coarse.packed().handle, self.fine.packed().handle,
                                                     self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K,
                                                     R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), hip.ptr(ws),
@@ -275,8 +308,8 @@ def cal_geometry(model_forward, samp_func, dataloader, args, device, sv_path=Non
 
 
 def _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_style_forward, latents_model_1,
-                  model_forward_fine, samp_func_fine, renderer):
-    """One batch of the stylised chain (rendering.py:118-178 == :280-327)."""
+                  model_forward_fine, samp_func_fine, renderer, min_weight=None):
+    """One batch of the stylised chain (rendering.py:118-178 == :280-327).  min_weight: RayRenderer.render's."""
     from . import utils
     rays_o, rays_d = b['rays_o'], b['rays_d']
     z = latents_model_1(style_ids=b['style_id'].long(), frame_ids=b['frame_id'].long(), type=args.dataset_type)
@@ -285,8 +318,10 @@ def _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_s
         # a dataset may deliver it per ray instead, so that the image does not depend on batching or sharding
         jitter = b['jitter'] if 'jitter' in b else torch.rand(rays_o.shape[0], args.N_samples, device=rays_o.device)
         out = renderer.render(rays_o, rays_d, args.N_samples, args.N_samples_fine, near=ds.near, far=ds.far,
-                              jitter=jitter, z=z)
+                              jitter=jitter, z=z, min_weight=min_weight)
         return out["rgb"], out["t"]
+    if min_weight is not None:
+        raise ValueError("min_weight needs renderer=RayRenderer(...): the per-stage chain has no culled form")
     R, L = rays_o.shape[0], z.shape[-1]
     zbar = torch.mean(z, dim=1, keepdim=True)                      # rendering.py:126
 
@@ -306,12 +341,13 @@ def _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_s
     return rgb_f, t_f
 
 
-def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer):
+def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None):
     """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
     `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
     style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
     hook (train_tgtcs.SyntheticScene): the rays this rank renders of each frame it takes part in -- its pixel range of
-    every frame under rays sharding, whole frames dealt round-robin under frames sharding."""
+    every frame under rays sharding, whole frames dealt round-robin under frames sharding.
+    min_weight: RayRenderer.render_latents' (None: the style networks run on every sample)."""
     ds = dataloader.dataset
     if renderer is None or not hasattr(ds, 'frame_batches'):
         raise ValueError("share_geometry needs renderer=RayRenderer(...) and a dataset with the frame_batches hook")
@@ -332,7 +368,7 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
                                               type=args.dataset_type) for sid in range(styles)])
             jitter = b['jitter'][sl] if 'jitter' in b else torch.rand(frame_ids.shape[0], args.N_samples, device=device)
             out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine, near=ds.near,
-                                          far=ds.far, jitter=jitter, zs=zs)
+                                          far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight)
             rgbs.append(out["rgb"].detach()), ts.append(out["t"].detach())
         have += R
         if have == res:           # a frame (this rank's part of it) is complete
@@ -349,11 +385,13 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
 
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
                  device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
-                 share_geometry=False):
+                 share_geometry=False, min_weight=None):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
     Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
-    share_geometry=True (not in the reference): all styles of a frame in one multi-latent call, see _render_style_shared."""
+    share_geometry=True (not in the reference): all styles of a frame in one multi-latent call, see _render_style_shared.
+    min_weight (not in the reference; needs `renderer`): the style networks only on the fine samples whose compositing
+    weight exceeds it, see RayRenderer.render_latents; None runs them on every sample."""
     _require_fine(args)
     latents_model_1.sigma_scale = sigma_scale
     if sv_path is not None:
@@ -361,14 +399,14 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     ds = dataloader.dataset
     ds.mode = 'valid_style'
     if share_geometry:
-        return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer)
+        return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0
     for batch in dataloader:
         b = _to_device(batch, device)
         rgb_f, t_f = _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_style_forward,
-                                   latents_model_1, model_forward_fine, samp_func_fine, renderer)
+                                   latents_model_1, model_forward_fine, samp_func_fine, renderer, min_weight=min_weight)
         pend_rgb = torch.cat([pend_rgb, rgb_f.detach().float()], 0)      # stays on the device until a frame is complete
         pend_t = torch.cat([pend_t, t_f.detach().float()], 0)
         while pend_rgb.shape[0] >= res:
@@ -387,10 +425,11 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
 
 def render_train_style(samp_func, model_forward, style_forward, concat_style_forward, latents_model_1, dataset, args,
                        device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0.,
-                       renderer=None):
+                       renderer=None, min_weight=None):
     """reference rendering.py:242-375: stylised render of the training views in `train_style` order; the batch is the
     largest divisor of h*w not above --chunk (:251-253); images already on disk are skipped (:267-270); RGB is clamped
-    to [0,1] (:328); depth is min-max normalised without epsilon and written as 3 channels (:358-361)."""
+    to [0,1] (:328); depth is min-max normalised without epsilon and written as 3 channels (:358-361).
+    min_weight: as in render_style."""
     _require_fine(args)
     os.makedirs(sv_path, exist_ok=True)
     latents_model_1.sigma_scale = sigma_scale
@@ -413,7 +452,7 @@ def render_train_style(samp_func, model_forward, style_forward, concat_style_for
         if not exists:
             b = _to_device(batch, device)
             rgb_f, t_f = _styled_batch(b, args, dataset, samp_func, model_forward, style_forward, concat_style_forward,
-                                       latents_model_1, model_forward_fine, samp_func_fine, renderer)
+                                       latents_model_1, model_forward_fine, samp_func_fine, renderer, min_weight=min_weight)
             rgbs.append(torch.clamp(rgb_f, 0., 1.).detach())
             ts.append(t_f.detach())
         it += 1

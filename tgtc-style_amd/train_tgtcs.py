@@ -263,7 +263,8 @@ def train(args):
                   samp_func_fine=utils.sampling_pts_fine_torch, args=args, device=device)
     styled = dict(style_forward=utils.batchify(lambda **kw: style_model(**kw), args.chunk),
                   concat_style_forward=utils.batchify(lambda **kw: concat_model(**kw), args.chunk),
-                  latents_model_1=latents, sigma_scale=args.sigma_scale, renderer=renderer)
+                  latents_model_1=latents, sigma_scale=args.sigma_scale, renderer=renderer,
+                  min_weight=args.cull_weight if args.cull_weight >= 0 else None)   # --cull_weight, default -1 = off
     with torch.no_grad():
         if args.render_valid_style:
             out = os.path.join(sv_path, 'render_valid_' + str(global_step))
