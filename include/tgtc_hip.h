@@ -267,6 +267,52 @@ int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc_net* fine,
                                    float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
                                    float* t_fine, uint32_t* live_count, void* stream);
 
+/* ------------------------------------------------------------------ restyle rays from a cached geometry
+ * Steps 1-4 of tgtc_render_rays_styled_sparse (geometry half, sigma pass, depth + weights, compaction) depend on the ray
+ * alone.  tgtc_geometry_build runs them once, tgtc_geometry_pack keeps what a later render needs as a compact device
+ * buffer, and tgtc_restyle_rays renders the same rays under new latents from that buffer: ONE launch of the compact form
+ * of the indexed multi-latent kernel over the cached list, ONE compositing launch over (latent, ray), one device copy of
+ * the depth image.  No coarse handle, no hipMemset, no dense per-sample plane.
+ * Identity: rgb_fine, t_fine of tgtc_restyle_rays are the BITS of tgtc_render_rays_styled_sparse with the build's
+ *   min_weight: a live sample is the same column of the same MFMA sequence on the same operands, and a sample that is not in
+ *   the list enters the dense compositing sum as acc + w x 0 or acc + 0 x c, which leaves acc unchanged.
+ * It is a mode the caller asks for; TGTC_PATH_AUTO never selects it.
+ *
+ * tgtc_geometry_build: `workspace` is the sparse workspace at K = 1, tgtc_render_styled_sparse_workspace_bytes(R, n_coarse,
+ *   n_fine, 1), in that layout; the depth image is also left in the first R floats of its colour plane, where the pack
+ *   reads it.  t_fine float [R] or NULL.  live_count: device pointer to ONE uint32, required: the caller reads it once (the
+ *   one synchronisation per build) to allocate the cache.  No style handle is involved.
+ * tgtc_geometry_pack: workspace of the build, count = the value read from live_count -> cache (device, at least
+ *   tgtc_geometry_cache_bytes(R, count) bytes).  Deterministic, no atomics.  Cache layout, every plane rounded up to 256 bytes:
+ *     header    256 bytes: uint32 words  0 magic 0x43475447 ("TGGC"), 1 layout version (1), 2-3 R (low, high), 4 N =
+ *               n_coarse + n_fine, 5 count, 6 the bits of min_weight, the rest 0
+ *     t_fine    float  [R]
+ *     ray_start uint32 [R+1]    list entries [ray_start[r], ray_start[r+1]) are the live samples of ray r
+ *     live      uint32 [count]  dense sample indices s = r x N + i, ascending
+ *     ts_live   float  [count]  ts_f[live]
+ *     w_live    float  [count]  w_f[live]
+ *   About 12 bytes per live sample + 8 per ray.  The buffer is position independent: it may be copied, saved and reloaded.
+ * tgtc_restyle_rays: z float [K,R,32], rgb_fine float [K,R,3], t_fine float [R] or NULL.  rays_o / rays_d, n_coarse, n_fine
+ *   and the fine handle must be those of the build (the cache stores depths, not positions).  workspace: at least
+ *   tgtc_restyle_workspace_bytes(count, K) bytes = rgb_live float [K,count,3] rounded up to 256 (may be NULL when count == 0).
+ *   count == 0: no style kernel is launched; rgb_fine is +0 and t_fine is copied.  The call reads the cache only.
+ * Both size functions return 0 for negative arguments (K < 1).
+ * Errors (every argument check returns before a device is touched): null pointers, K < 1, R < 0, count < 0, wrong handle
+ *   kinds, fine and style handles of different precisions, min_weight < 0 or NaN, n_coarse < 3, n_fine < 1, a cache or
+ *   workspace below its size function, count > R x N -> TGTC_ERR_ARG;  R x N >= 2^31 or K x count >= 2^31 ->
+ *   TGTC_ERR_UNSUPPORTED;  R == 0 -> TGTC_OK.
+ * Scratch slab: tgtc_restyle_rays uses both slab regions of the STYLE HANDLE; launches on one style handle must not overlap. */
+int tgtc_geometry_build(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R,
+                        int n_coarse, int n_fine, float near_, float far_, const float* jitter, float min_weight,
+                        void* workspace, size_t workspace_bytes, float* t_fine, uint32_t* live_count, void* stream);
+size_t tgtc_geometry_cache_bytes(int64_t R, int64_t count);
+int tgtc_geometry_pack(const void* workspace, int64_t R, int n_coarse, int n_fine, float min_weight, int64_t count,
+                       void* cache, size_t cache_bytes, void* stream);
+size_t tgtc_restyle_workspace_bytes(int64_t count, int K);
+int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
+                      int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
+                      void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ EXTRA = {
     "synthetic_styles": (int, 1),      # styles of the synthetic scene's latent table (1: one style)
     "share_geometry": (None, False),   # --render_valid_style: all styles of a frame in ONE multi-latent call (HELP below)
     "cull_weight": (float, -1.0),      # stylised renders: style networks only where the compositing weight exceeds it (HELP below)
+    "geometry_cache": (str, ""),       # --share_geometry: directory of cached ray geometry, reused across runs (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
 }
@@ -61,6 +62,13 @@ HELP = {
                    "over all samples.  0 reproduces the image of the chain of per-sample kernels bit for bit (samples of "
                    "weight exactly 0 add +0 to a pixel); a positive value bounds the change of each ray by the sum of its "
                    "dropped weights and leaves the depth image alone.  Default -1: off, every sample is styled",
+    "geometry_cache": "with --render_valid_style --share_geometry (required; refused otherwise): a directory that keeps the "
+                      "ray-only half of every frame (fine depths, the list of samples with compositing weight above "
+                      "--cull_weight, their depths and weights; about 12 bytes per live sample).  A frame whose file is "
+                      "there and was built for the same camera, pixel range, sample counts, jitter seed, NeRF checkpoint "
+                      "step, precisions and --cull_weight is restyled from it without any NeRF density pass; otherwise it "
+                      "is built and saved.  The images are those of the run without the cache, bit for bit.  An unset "
+                      "--cull_weight means 0 here",
 }
 
 

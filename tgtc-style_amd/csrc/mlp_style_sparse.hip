@@ -14,6 +14,13 @@
 //                                                 index as there; rgb[k,s] is scattered to its dense position (the caller
 //                                                 zero-fills the planes); sigma is not written.  The number of tiles comes
 //                                                 from n_live read on the device.
+//   styled_rays_sparse_kernel<C, true>            the COMPACT form of the same body (tgtc_restyle_rays, render.hip): the list,
+//                                                 the depth of every list entry (ts_live[i] = ts[live[i]]) and the list's
+//                                                 length (a host value) come from a geometry cache; rgb[k,i] goes to the
+//                                                 compact plane [K,count,3] at the sample's LIST position.  No dense plane is
+//                                                 read or written.  Everything else -- r = live[i] / N, z[k,r], o + t d, the
+//                                                 MFMA sequence, the clamped columns masked from every store -- is shared
+//                                                 source, so a live sample has the bits it has in the scattered form.
 //
 // Per latent this is the MFMA sequence of styled_rays_multi_kernel on the same operands, and a column (sample) of an MFMA
 // does not depend on the other columns of its tile, so a live sample carries the bits of the dense kernels.
@@ -32,17 +39,19 @@ struct StyledSparseArgs {
     const char* style_stream;
     char* stash;             // region A: gridDim.x * kStashBytesPerWG
     long long stash2_delta;  // region B of a workgroup lies this many bytes behind its region A
-    long long M;             // R * N samples (per latent)
+    long long M;             // samples per colour plane: R * N (scattered form), the list's length (compact form)
     long long R;
     int N;
     int K;
     const double* rays_o;
     const double* rays_d;
-    const float* ts;
+    const float* ts;           // [R,N]; the compact form reads ts_live instead
     const float* z;            // [K,R,32]
     const unsigned* live;      // [n_live] ascending sample indices
-    const unsigned* n_live;    // device scalar
-    float* rgb;                // [K,R,N,3], zero-filled by the caller
+    const unsigned* n_live;    // device scalar; the compact form takes `count`
+    float* rgb;                // [K,R,N,3], zero-filled by the caller; compact form: [K,count,3], every entry written
+    const float* ts_live;      // compact form: [count] depths of the list's samples
+    unsigned count;            // compact form: the list's length
 };
 
 // concat | style, both chunk aligned (as PairMap of mlp_style_multi.hip)
@@ -56,7 +65,7 @@ struct SparsePairMap {
     static_assert(kConcatFrags % C::FPC == 0, "concat stream must end on a chunk boundary");
 };
 
-template <class C>
+template <class C, bool COMPACT>
 __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_sparse_kernel(StyledSparseArgs a) {
     constexpr int NCT = C::NCT;
     constexpr bool SPLIT = C::SPLIT;
@@ -66,7 +75,9 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
 
     // the list's length decides the tiles; a workgroup without one leaves before any LDS-DMA is issued (none may be in
     // flight when it ends), which is also what keeps live[n_live - 1] from being read when nothing is live
-    const unsigned n_live = *a.n_live;
+    unsigned n_live;
+    if constexpr (COMPACT) n_live = a.count;
+    else n_live = *a.n_live;
     const unsigned n_tiles = (n_live + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;   // n_live < 2^31
     if (blockIdx.x >= n_tiles) return;
 
@@ -109,7 +120,7 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
             const unsigned s = a.live[i];
             sidx[c] = s;
             const long long r = s / (unsigned)a.N;
-            const double t = (double)a.ts[s];
+            const double t = (double)(COMPACT ? a.ts_live[i] : a.ts[s]);
 #pragma unroll
             for (int k = 0; k < 3; ++k) pos[c][k] = a.rays_o[r * 3 + k] + t * a.rays_d[r * 3 + k];
             // retire the loads before any LDS-DMA is issued (their wait would drain the whole prefetch)
@@ -224,15 +235,17 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
                     });
             }
             stash_load<C>(slab, Xh, Xl);
-            // ---- style layers 1..7 -> rgb[k], scattered to the sample's dense position (models.py:172-179)
+            // ---- style layers 1..7 -> rgb[k], scattered to the sample's dense position (models.py:172-179); the compact
+            //      form writes the column's list position, rebuilt from the tile (own masks the clamped columns)
             float* rgb_k = a.rgb + (long long)k * a.M * 3;
             style_tail<C, Map::F_STYLE, kConcatBiasFloats>(ws, pair_bias, pe_h, pe_l, zb_h, zb_l, Xh, Xl, Yh, Yl,
                                                            [&](auto c_, auto h_, const float4v& acc) {
                                                                constexpr int c = decltype(c_)::value, hf = decltype(h_)::value;
                                                                if (g == 0 && (own >> c & 1)) {
+                                                                   const unsigned at = COMPACT ? i_wave + c * 16 + n : sidx[c];
 #pragma unroll
                                                                    for (int r = 2 * hf; r < (hf ? 3 : 2); ++r)
-                                                                       rgb_k[(size_t)sidx[c] * 3 + r] = 1.0f / (1.0f + expf(-acc[r]));
+                                                                       rgb_k[(size_t)at * 3 + r] = 1.0f / (1.0f + expf(-acc[r]));
                                                                }
                                                            });
         }
@@ -242,17 +255,25 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
 using CfgFast = MlpCfg<8, 2, false, 4>;  // the geometries of styled_rays_multi_kernel
 using CfgExact = MlpCfg<8, 1, true, 4>;
 
-// The fp16 instance is compiled in a translation unit of its own (this source with -DTGTC_TU_FP16_ONLY) so that the two
-// kernels build in parallel.
-template <class C>
+// Each of the four instances (fp16x3 / fp16, scattered / compact) is compiled in a translation unit of its own -- this
+// source as it is, with -DTGTC_TU_FP16_ONLY, -DTGTC_TU_COMPACT or both -- so that the kernels build in parallel.
+template <class C, bool COMPACT>
 void launch_styled_rays_sparse(unsigned grid, const StyledSparseArgs& a, hipStream_t st) {
-    styled_rays_sparse_kernel<C><<<grid, C::NWAVES * 64, 0, st>>>(a);
+    styled_rays_sparse_kernel<C, COMPACT><<<grid, C::NWAVES * 64, 0, st>>>(a);
 }
-#ifdef TGTC_TU_FP16_ONLY
-template void launch_styled_rays_sparse<CfgFast>(unsigned, const StyledSparseArgs&, hipStream_t);
+#if defined(TGTC_TU_FP16_ONLY) && defined(TGTC_TU_COMPACT)
+template void launch_styled_rays_sparse<CfgFast, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+}  // namespace tgtc
+#elif defined(TGTC_TU_COMPACT)
+template void launch_styled_rays_sparse<CfgExact, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+}  // namespace tgtc
+#elif defined(TGTC_TU_FP16_ONLY)
+template void launch_styled_rays_sparse<CfgFast, false>(unsigned, const StyledSparseArgs&, hipStream_t);
 }  // namespace tgtc
 #else
-extern template void launch_styled_rays_sparse<CfgFast>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, false>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------ compaction
 // The plane of M weights is cut into kCompactParts contiguous ranges of `span` samples (a multiple of the block size).
@@ -375,14 +396,37 @@ int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style,
     a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.z = z, a.live = live, a.n_live = n_live, a.rgb = rgb;
     if (nerf->precision == TGTC_PREC_FP16) {
         const long long tiles = (a.M + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
-        launch_styled_rays_sparse<CfgFast>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+        launch_styled_rays_sparse<CfgFast, false>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
     } else {
         const long long tiles = (a.M + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
-        launch_styled_rays_sparse<CfgExact>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+        launch_styled_rays_sparse<CfgExact, false>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    }
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+// rgb_live[k, i] for the `count` samples of a cached list (count >= 1; K x count < 2^31 and the precisions are checked by the
+// caller, tgtc_restyle_rays): the compact form, its grid sized from the host count.
+int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                             const float* z, int K, int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count,
+                             float* rgb_live, hipStream_t st) {
+    StyledSparseArgs a{};
+    a.nerf_bias = nerf->dev, a.nerf_stream = nerf->dev + nerf->bias_bytes;
+    a.pair_bias = style->dev, a.concat_stream = style->dev + style->bias_bytes;
+    a.style_stream = style->dev + style->stream2_off;
+    a.stash = style->dev + style->stash_off, a.stash2_delta = (long long)(style->stash2_off - style->stash_off);
+    a.M = count, a.R = R, a.N = N, a.K = K;
+    a.rays_o = rays_o, a.rays_d = rays_d, a.z = z, a.live = live, a.ts_live = ts_live, a.count = (unsigned)count, a.rgb = rgb_live;
+    if (nerf->precision == TGTC_PREC_FP16) {
+        const long long tiles = (count + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgFast, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    } else {
+        const long long tiles = (count + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgExact, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
     }
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;
 }
 
 }  // namespace tgtc
-#endif  // TGTC_TU_FP16_ONLY
+#endif  // TGTC_TU_FP16_ONLY || TGTC_TU_COMPACT

@@ -6,6 +6,8 @@
 // and LDS staging of the per-ray sample buffers.  The arithmetic follows the reference's evaluation
 // order (no FMA contraction where the reference has separate roundings) so float64 outputs agree to
 // the last bits and float32 outputs to ~1 ulp.
+#include <algorithm>
+
 #include "common.h"
 #include "raymarch_wave.h"
 
@@ -116,6 +118,10 @@ __global__ void __launch_bounds__(256) posenc_kernel(const T* __restrict__ x, lo
 // every lane walks the whole chain with the `keep` factors broadcast lane by lane, so the weights do not depend
 // on the tiling (raymarch_wave.h composite_tile computes the same chain 16 samples at a time).  Then four weighted
 // wave reductions.
+// acc + w * c of one colour channel: ONE expression for composite_wave and composite_live_kernel, so that the compiler
+// contracts (or does not contract) it the same way in both.
+__device__ __forceinline__ float composite_accumulate(float acc, float w, float c) { return acc + w * c; }
+
 template <int C>
 __device__ __forceinline__ void composite_wave(const float* __restrict__ rgb, const float* __restrict__ sigma,
                                                const float* __restrict__ ts, int N, float* rgb_exp, float* t_exp,
@@ -156,9 +162,9 @@ __device__ __forceinline__ void composite_wave(const float* __restrict__ rgb, co
             wsum = wsum + w;
             if (weights) weights[i] = w;
             if (rgb) {  // wave-uniform: the sigma-only coarse pass of a fused render has no colours
-                acc[0] = acc[0] + w * rgb[i * 3 + 0];
-                acc[1] = acc[1] + w * rgb[i * 3 + 1];
-                acc[2] = acc[2] + w * rgb[i * 3 + 2];
+                acc[0] = composite_accumulate(acc[0], w, rgb[i * 3 + 0]);
+                acc[1] = composite_accumulate(acc[1], w, rgb[i * 3 + 1]);
+                acc[2] = composite_accumulate(acc[2], w, rgb[i * 3 + 2]);
             }
             acc[3] = acc[3] + w * tv[k];
         }
@@ -279,6 +285,98 @@ __global__ void __launch_bounds__(256) composite_kernel(const float* __restrict_
     composite_wave<C>(rgb ? rgb + r * N * 3 : nullptr, sigma + r * N, ts + r * N, N,
                       rgb_exp ? rgb_exp + r * 3 : nullptr, t_exp ? t_exp + r : nullptr,
                       weights ? weights + r * N : nullptr, noise ? noise + r * N : nullptr, white_bkgd);
+}
+
+// ------------------------------------------------------------------------------------ geometry cache
+// composite_wave's colour sums from a compact list (tgtc_restyle_rays, render.hip).  One wavefront per (latent k, ray r).
+// The ray's live samples are the list entries [ray_start[r], ray_start[r+1]) (ascending dense indices s = r * N + i); lane l
+// takes those with i in [l*C, l*C+C) -- the run it owns in composite_wave -- in ascending order into accumulators that start
+// at 0, then the same xor butterfly.  A sample that is not in the list enters composite_wave's run as acc + w * 0 (its
+// colour plane entry is +0) or acc + 0 * c (its weight is 0), which leaves acc unchanged with or without contraction:
+// skipping it changes no bit.  w_live[j] = the weight composite_wave computes for the sample, colours rgb_live [K,count,3].
+template <int C>
+__global__ void __launch_bounds__(256) composite_live_kernel(const unsigned* __restrict__ ray_start,
+                                                             const unsigned* __restrict__ live,
+                                                             const float* __restrict__ w_live,
+                                                             const float* __restrict__ rgb_live, long long R, int N, int K,
+                                                             long long count, float* __restrict__ rgb_exp) {
+    const long long id = (long long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (id >= (long long)K * R) return;  // wave-uniform
+    const long long k = id / R, r = id - k * R;
+    const int lane = threadIdx.x & 63;
+    const unsigned j1 = ray_start[r + 1];
+    const unsigned base = (unsigned)(r * N);              // R * N < 2^31
+    const unsigned first = base + (unsigned)(lane * C);   // this lane's run [first, last); lane * C <= 504
+    const unsigned last = min(first + (unsigned)C, base + (unsigned)N);
+    unsigned lo = ray_start[r], hi = j1;                  // first list entry of the ray that is >= first
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (live[mid] < first) lo = mid + 1; else hi = mid;
+    }
+    const float* __restrict__ c = rgb_live + k * count * 3;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int q = 0; q < C; ++q) {
+        const unsigned j = lo + (unsigned)q;
+        if (j >= j1 || live[j] >= last) break;
+        const float w = w_live[j];
+        acc[0] = composite_accumulate(acc[0], w, c[(size_t)j * 3 + 0]);
+        acc[1] = composite_accumulate(acc[1], w, c[(size_t)j * 3 + 1]);
+        acc[2] = composite_accumulate(acc[2], w, c[(size_t)j * 3 + 2]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[j] = acc[j] + __shfl_xor(acc[j], off);
+    }
+    if (lane == 0) rgb_exp[id * 3 + 0] = acc[0], rgb_exp[id * 3 + 1] = acc[1], rgb_exp[id * 3 + 2] = acc[2];
+}
+
+// tgtc_geometry_pack: the planes of a geometry cache out of the culled render's workspace, one thread per entry of the
+// longest plane.  ray_start[r] = the number of list entries below r * N (a binary search; r = R gives count).  A list entry
+// outside the sample range (a `count` above the list's real length reads words no build wrote) is stored as sample 0.
+struct GeometryPackArgs {
+    const unsigned* live;   // the workspace's list
+    const float* ts_f;      // [R,N]
+    const float* w_f;       // [R,N]
+    const float* t_fine;    // [R]
+    long long R;
+    int N;
+    unsigned count;
+    unsigned min_weight_bits;
+    unsigned* header;       // kGeometryHeaderWords
+    float* t_out;
+    unsigned* ray_start;
+    unsigned* live_out;
+    float* ts_live;
+    float* w_live;
+};
+constexpr unsigned kGeometryMagic = 0x43475447u;   // "TGGC"
+constexpr unsigned kGeometryVersion = 1;
+constexpr int kGeometryHeaderWords = 64;
+
+__global__ void __launch_bounds__(256) geometry_pack_kernel(GeometryPackArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < kGeometryHeaderWords) {
+        const unsigned long long R = (unsigned long long)a.R;
+        const unsigned words[8] = {kGeometryMagic, kGeometryVersion, (unsigned)R, (unsigned)(R >> 32), (unsigned)a.N, a.count,
+                                   a.min_weight_bits, 0u};
+        a.header[i] = i < 8 ? words[i] : 0u;
+    }
+    if (i < a.R) a.t_out[i] = a.t_fine[i];
+    if (i <= a.R) {
+        const unsigned key = (unsigned)(i * a.N);   // <= R * N < 2^31
+        unsigned lo = 0, hi = a.count;
+        while (lo < hi) {
+            const unsigned mid = (lo + hi) >> 1;
+            if (a.live[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        a.ray_start[i] = lo;
+    }
+    if (i < a.count) {
+        unsigned s = a.live[i];
+        if (s >= (unsigned)(a.R * a.N)) s = 0;
+        a.live_out[i] = s, a.ts_live[i] = a.ts_f[s], a.w_live[i] = a.w_f[s];
+    }
 }
 
 // ------------------------------------------------------------------------------------ fine sampling
@@ -486,6 +584,36 @@ int launch_composite_ex(const float* rgb, const float* sigma, const float* ts, i
 int launch_composite(const float* rgb, const float* sigma, const float* ts, int64_t R, int N, float* rgb_exp,
                      float* t_exp, float* weights, hipStream_t st) {
     return launch_composite_ex(rgb, sigma, ts, R, N, rgb_exp, t_exp, weights, st, nullptr, 0);
+}
+
+// rgb_exp [K,R,3] from a geometry cache's list planes and the compact colours; the lane runs are launch_composite_ex's.
+int launch_composite_live(const uint32_t* ray_start, const uint32_t* live, const float* w_live, const float* rgb_live, int64_t R,
+                          int N, int K, int64_t count, float* rgb_exp, hipStream_t st) {
+    const unsigned nb = blocks_for((long long)K * R, 4);
+    const int C = (N + 63) / 64;
+#define TGTC_COMPOSITE_LIVE(CC) composite_live_kernel<CC><<<nb, 256, 0, st>>>(ray_start, live, w_live, rgb_live, R, N, K, count, rgb_exp)
+    switch (C) {
+        case 1: TGTC_COMPOSITE_LIVE(1); break;
+        case 2: TGTC_COMPOSITE_LIVE(2); break;
+        case 3: TGTC_COMPOSITE_LIVE(3); break;
+        case 4: TGTC_COMPOSITE_LIVE(4); break;
+        case 5: case 6: case 7: case 8: TGTC_COMPOSITE_LIVE(8); break;
+        default: return fail(TGTC_ERR_UNSUPPORTED, "composite_live: N=%d samples per ray exceeds 512", N);
+    }
+#undef TGTC_COMPOSITE_LIVE
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w_f, const float* t_fine, int64_t R, int N,
+                         int64_t count, float min_weight, uint32_t* header, float* t_out, uint32_t* ray_start, uint32_t* live_out,
+                         float* ts_live, float* w_live, hipStream_t st) {
+    GeometryPackArgs a{live, ts_f, w_f, t_fine, R, N, (unsigned)count, __builtin_bit_cast(unsigned, min_weight),
+                       header, t_out, ray_start, live_out, ts_live, w_live};
+    const long long longest = std::max<long long>({count, R + 1, kGeometryHeaderWords});
+    geometry_pack_kernel<<<blocks_for(longest, 256), 256, 0, st>>>(a);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
 }
 
 int launch_composite_backward(const float* rgb, const float* sigma, const float* ts, const float* noise, int64_t R, int N,

@@ -29,6 +29,15 @@ int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style,
 int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
                         hipStream_t st);
 
+int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                             const float* z, int K, int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count,
+                             float* rgb_live, hipStream_t st);
+int launch_composite_live(const uint32_t* ray_start, const uint32_t* live, const float* w_live, const float* rgb_live, int64_t R,
+                          int N, int K, int64_t count, float* rgb_exp, hipStream_t st);
+int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w_f, const float* t_fine, int64_t R, int N,
+                         int64_t count, float min_weight, uint32_t* header, float* t_out, uint32_t* ray_start, uint32_t* live_out,
+                         float* ts_live, float* w_live, hipStream_t st);
+
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RenderWorkspace {
@@ -88,6 +97,29 @@ struct SparseWorkspace {
         live = reinterpret_cast<uint32_t*>(base + m.total + plane);
         scratch = reinterpret_cast<uint32_t*>(base + m.total + 2 * plane);
         total = m.total + 2 * plane + kSparseScratchBytes;
+    }
+};
+
+// A geometry cache (tgtc_geometry_pack): a 256-byte header, then t_fine [R], ray_start [R+1], live / ts_live / w_live [count],
+// every plane rounded up to 256 bytes.
+struct GeometryCacheLayout {
+    uint32_t *header, *ray_start, *live;
+    float *t, *ts_live, *w_live;
+    size_t total;
+    GeometryCacheLayout(char* base, int64_t R, int64_t count) {
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            char* p = base + off;
+            off += align256(bytes);
+            return p;
+        };
+        header = reinterpret_cast<uint32_t*>(take(256));
+        t = reinterpret_cast<float*>(take((size_t)R * 4));
+        ray_start = reinterpret_cast<uint32_t*>(take(((size_t)R + 1) * 4));
+        live = reinterpret_cast<uint32_t*>(take((size_t)count * 4));
+        ts_live = reinterpret_cast<float*>(take((size_t)count * 4));
+        w_live = reinterpret_cast<float*>(take((size_t)count * 4));
+        total = off;
     }
 };
 }  // namespace tgtc
@@ -284,6 +316,42 @@ extern "C" size_t tgtc_render_styled_sparse_workspace_bytes(int64_t R, int n_coa
     return SparseWorkspace(nullptr, R, n_coarse, n_fine, K).total;
 }
 
+// Steps 1-4 of the culled stylised render, the half that depends on the ray alone (tgtc_render_rays_styled_sparse and
+// tgtc_geometry_build): fine depths ts_f, sigma_f, the depth image, the weights plane w_f, the ascending list live[] of the
+// samples with w_f > min_weight and its length (scratch word 0, and *live_count where given).
+static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R,
+                        int n_coarse, int n_fine, float near_, float far_, const float* jitter, float min_weight,
+                        const SparseWorkspace& sw, float* t_fine, uint32_t* live_count, void* stream) {
+    const MultiWorkspace& ws = sw.m;
+    const int nt = n_coarse + n_fine;
+    hipStream_t st = as_stream(stream);
+    int rc;
+    // 1. geometry half, as tgtc_render_rays_styled_multi
+    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
+        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
+        rc = launch_fused_depths(coarse->precision, a, st);
+        if (rc) return rc;
+    } else {
+        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
+        if (rc) return rc;
+        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
+        if (rc) return rc;
+        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
+        if (rc) return rc;
+        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+        if (rc) return rc;
+    }
+    // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
+    //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
+    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
+    if (rc) return rc;
+    // 3. depth image and the weights plane
+    rc = launch_composite(nullptr, ws.sigma_f, ws.ts_f, R, nt, nullptr, t_fine, sw.w_f, st);
+    if (rc) return rc;
+    // 4. the ascending list of samples with w > min_weight
+    return launch_compact_live(sw.w_f, R * (int64_t)nt, min_weight, sw.live, sw.scratch, live_count, st);
+}
+
 // The multi-latent stylised render with the style networks only on the samples whose compositing weight exceeds
 // min_weight: geometry half as above, a sigma-only pass of the fine NeRF over every sample, the existing compositing kernel
 // for depth + weights, the compaction, then the indexed multi-latent kernel (mlp_style_sparse.hip) into zero-filled colour
@@ -311,31 +379,9 @@ extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc
                  sw.total);
     const MultiWorkspace& ws = sw.m;
     hipStream_t st = as_stream(stream);
-    int rc;
-    // 1. geometry half, as tgtc_render_rays_styled_multi
-    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
-        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
-        rc = launch_fused_depths(coarse->precision, a, st);
-        if (rc) return rc;
-    } else {
-        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
-        if (rc) return rc;
-        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
-        if (rc) return rc;
-        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
-        if (rc) return rc;
-        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
-        if (rc) return rc;
-    }
-    // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
-    //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
-    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
-    if (rc) return rc;
-    // 3. depth image and the weights plane
-    rc = launch_composite(nullptr, ws.sigma_f, ws.ts_f, R, nt, nullptr, t_fine, sw.w_f, st);
-    if (rc) return rc;
-    // 4. the ascending list of samples with w > min_weight
-    rc = launch_compact_live(sw.w_f, R * (int64_t)nt, min_weight, sw.live, sw.scratch, live_count, st);
+    // 1-4. everything that depends on the ray alone
+    int rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine,
+                          live_count, stream);
     if (rc) return rc;
     // 5. dead samples keep colour +0
     TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
@@ -348,5 +394,99 @@ extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc
                               nullptr, st);
         if (rc) return rc;
     }
+    return TGTC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ geometry cache + restyle
+// The ray-only half of the culled render kept as a compact device buffer, and "the same rays under new latents" from it:
+// one launch of the compact indexed kernel over the cached list, one compositing launch over (latent, ray).
+
+// Steps 1-4 of tgtc_render_rays_styled_sparse on the sparse workspace at K = 1.  The depth image also stays in the
+// workspace (the first R floats of the colour plane, which no step of the build uses), where tgtc_geometry_pack reads it.
+extern "C" int tgtc_geometry_build(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
+                                   int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                   float min_weight, void* workspace, size_t workspace_bytes, float* t_fine,
+                                   uint32_t* live_count, void* stream) {
+    TGTC_REQUIRE(min_weight >= 0.0f, "geometry_build: min_weight must be >= 0 and not NaN (got %g)", (double)min_weight);
+    TGTC_REQUIRE(coarse && fine && R >= 0, "geometry_build: bad argument");
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0, "geometry_build: coarse and fine must be NeRF handles");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && workspace && live_count, "geometry_build: null pointer");
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_build: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, 1);
+    TGTC_REQUIRE(workspace_bytes >= sw.total, "geometry_build: workspace of %zu bytes, need %zu", workspace_bytes, sw.total);
+    int rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, sw.m.rgb_f,
+                          live_count, stream);
+    if (rc) return rc;
+    if (t_fine)
+        TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, sw.m.rgb_f, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return TGTC_OK;
+}
+
+extern "C" size_t tgtc_geometry_cache_bytes(int64_t R, int64_t count) {
+    if (R < 0 || count < 0) return 0;
+    return GeometryCacheLayout(nullptr, R, count).total;
+}
+
+extern "C" int tgtc_geometry_pack(const void* workspace, int64_t R, int n_coarse, int n_fine, float min_weight, int64_t count,
+                                  void* cache, size_t cache_bytes, void* stream) {
+    TGTC_REQUIRE(min_weight >= 0.0f, "geometry_pack: min_weight must be >= 0 and not NaN (got %g)", (double)min_weight);
+    TGTC_REQUIRE(R >= 0 && count >= 0, "geometry_pack: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    TGTC_REQUIRE(workspace && cache, "geometry_pack: null pointer");
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_pack: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt, "geometry_pack: count %lld exceeds the %lld samples", (long long)count, (long long)(R * nt));
+    GeometryCacheLayout gc(static_cast<char*>(cache), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "geometry_pack: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    SparseWorkspace sw(static_cast<char*>(const_cast<void*>(workspace)), R, n_coarse, n_fine, 1);
+    return launch_geometry_pack(sw.live, sw.m.ts_f, sw.w_f, sw.m.rgb_f, R, nt, count, min_weight, gc.header, gc.t, gc.ray_start,
+                                gc.live, gc.ts_live, gc.w_live, as_stream(stream));
+}
+
+extern "C" size_t tgtc_restyle_workspace_bytes(int64_t count, int K) {
+    if (count < 0 || K < 1) return 0;
+    return align256((size_t)K * (size_t)count * 3 * sizeof(float));
+}
+
+extern "C" int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                 const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                                 size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                 float* t_fine, void* stream) {
+    TGTC_REQUIRE(K >= 1, "restyle_rays: need K >= 1 latent sets (got %d)", K);
+    TGTC_REQUIRE(fine && style && R >= 0 && count >= 0, "restyle_rays: bad argument");
+    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays: fine must be a NeRF handle, style a style handle");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    TGTC_REQUIRE(fine->precision == style->precision,
+                 "restyle_rays: fine NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays: null pointer");
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt, "restyle_rays: count %lld exceeds the %lld samples", (long long)count, (long long)(R * nt));
+    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays: K x count >= 2^31 (fewer latents per call)");
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    const size_t need = tgtc_restyle_workspace_bytes(count, K);
+    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    float* rgb_live = static_cast<float*>(workspace);
+    int rc;
+    // 1. trunk + concat MLP + style MLP over the cached list into the compact colour planes (nothing to launch for an empty list)
+    if (count > 0) {
+        rc = styled_restyle_live_impl(fine, style, rays_o, rays_d, z, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        if (rc) return rc;
+    }
+    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
+    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
+    if (rc) return rc;
+    // 3. the depth image
+    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
     return TGTC_OK;
 }

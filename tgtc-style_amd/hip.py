@@ -64,7 +64,8 @@ _SIGNATURES = {
 }
 _RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_render_workspace_bytes": c_size_t,
              "tgtc_render_styled_multi_workspace_bytes": c_size_t,
-             "tgtc_render_styled_sparse_workspace_bytes": c_size_t}
+             "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
+             "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t}
 _OPTIONAL = {
     "tgtc_style_create": [ctypes.POINTER(Linear), c_int, ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],
     "tgtc_concat_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
@@ -83,6 +84,13 @@ _OPTIONAL = {
     "tgtc_render_rays_styled_sparse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                        c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p,
                                        c_void_p, c_void_p],
+    "tgtc_geometry_build": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_float,
+                            c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_geometry_cache_bytes": [c_int64, c_int64],
+    "tgtc_geometry_pack": [c_void_p, c_int64, c_int, c_int, c_float, c_int64, c_void_p, c_size_t, c_void_p],
+    "tgtc_restyle_workspace_bytes": [c_int64, c_int],
+    "tgtc_restyle_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
+                          c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
 }
 
 

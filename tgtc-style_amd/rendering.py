@@ -15,6 +15,69 @@ import torch
 from . import hip
 
 
+class GeometryCache:
+    """The ray-only half of a culled stylised render (tgtc_geometry_build + tgtc_geometry_pack): one flat uint8 buffer in the
+    layout include/tgtc_hip.h documents -- a 256-byte header, t [R], ray_start [R+1], live / ts_live / w_live [count], every
+    plane rounded up to 256 bytes -- plus the metadata a restyle is checked against.  `key` is any string the caller uses
+    to tell caches apart (None: unchecked)."""
+    MAGIC, VERSION = 0x43475447, 1
+
+    def __init__(self, buffer, R, N, count, min_weight, key=None, n_coarse=None, n_fine=None):
+        self.buffer, self.R, self.N, self.count = buffer, int(R), int(N), int(count)
+        self.min_weight, self.key = float(min_weight), key
+        self.n_coarse, self.n_fine = n_coarse, n_fine
+        if buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.numel() < self.nbytes(self.R, self.count):
+            raise ValueError("GeometryCache: the buffer must be uint8 [>= %d] for R = %d, count = %d"
+                             % (self.nbytes(self.R, self.count), self.R, self.count))
+
+    @staticmethod
+    def _planes(R, count):
+        """name -> (byte offset, words); the total size in bytes."""
+        up = lambda words: (4 * words + 255) // 256 * 256
+        out, off = {}, 256
+        for name, words in (("t", R), ("ray_start", R + 1), ("live", count), ("ts_live", count), ("w_live", count)):
+            out[name] = (off, words)
+            off += up(words)
+        return out, off
+
+    @classmethod
+    def nbytes(cls, R, count):
+        return cls._planes(R, count)[1]
+
+    def _view(self, name, dtype):
+        off, words = self._planes(self.R, self.count)[0][name]
+        return self.buffer[off:off + 4 * words].view(dtype)
+
+    header = property(lambda self: self.buffer[:256].view(torch.int32))
+    t = property(lambda self: self._view("t", torch.float32))
+    ray_start = property(lambda self: self._view("ray_start", torch.int32))      # the library's uint32, < 2^31
+    live = property(lambda self: self._view("live", torch.int32))
+    ts_live = property(lambda self: self._view("ts_live", torch.float32))
+    w_live = property(lambda self: self._view("w_live", torch.float32))
+
+    def save(self, path):
+        """One file: the buffer (moved to the host) and the metadata."""
+        torch.save({"buffer": self.buffer.detach().cpu(), "R": self.R, "N": self.N, "count": self.count,
+                    "min_weight": self.min_weight, "key": self.key, "n_coarse": self.n_coarse, "n_fine": self.n_fine}, path)
+
+    @classmethod
+    def load(cls, path, device):
+        """The cache of `save` on `device`.  ValueError if the header in the buffer contradicts the metadata or the list
+        leaves the sample range (a damaged file must not reach the kernels)."""
+        d = torch.load(path, map_location="cpu")
+        c = cls(d["buffer"].contiguous(), d["R"], d["N"], d["count"], d["min_weight"], d["key"], d["n_coarse"], d["n_fine"])
+        want = [cls.MAGIC, cls.VERSION, c.R & 0xffffffff, c.R >> 32, c.N, c.count,
+                int(np.float32(c.min_weight).view(np.uint32))]
+        want = [w - (1 << 32) if w >= 1 << 31 else w for w in want]
+        if c.header[:7].tolist() != want:
+            raise ValueError("GeometryCache.load: %s: the buffer's header does not match R, N, count, min_weight" % path)
+        if c.count and not (0 <= int(c.live.min()) and int(c.live.max()) < c.R * c.N and int(c.ray_start[-1]) == c.count
+                            and int(c.ray_start.min()) >= 0 and int(c.ray_start.max()) <= c.count):
+            raise ValueError("GeometryCache.load: %s: the list leaves the sample range" % path)
+        c.buffer = c.buffer.to(device)
+        return c
+
+
 class RayRenderer:
     """Fused renderer over packed networks.
 
@@ -33,6 +96,7 @@ class RayRenderer:
         self.coarse, self.fine, self.style, self.fused = coarse, fine, style, fused
         self._ws = None
         self._ws_multi = None
+        self._ws_restyle = None
 
     _REQUEST = {True: hip.PATH_AUTO, "single": hip.PATH_RAY_KERNEL, False: hip.PATH_CHAIN}
 
@@ -167,6 +231,75 @@ class RayRenderer:
                                                     R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), hip.ptr(ws),
                                                     ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
         return {"rgb": rgb, "t": t}
+
+    def build_geometry(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, min_weight=0., key=None):
+        """Everything of `render_latents(..., min_weight=min_weight)` that depends on the rays alone -- coarse pass, fine
+        depths, sigma pass, weights, compaction -- as a GeometryCache (about 12 bytes per live sample + 8 per ray).  The
+        host reads the live count once here (one synchronisation per build); `restyle` has none."""
+        hip.require_gpu(rays_o, rays_d)
+        lib = hip.load()
+        if n_fine <= 0:
+            raise ValueError("N_samples_fine must be > 0 (the reference render paths dereference None otherwise)")
+        min_weight = float(min_weight)
+        if not min_weight >= 0:
+            raise ValueError("min_weight must be >= 0 (got %r)" % min_weight)
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        R, dev = rays_o.shape[0], rays_o.device
+        need = lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, 1)
+        if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
+            self._ws_multi = None
+            self._ws_multi = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        ws = self._ws_multi
+        if jitter is not None:
+            jitter = jitter.to(torch.float32).contiguous()
+        live = torch.zeros((), device=dev, dtype=torch.int32)
+        hip.check(lib.tgtc_geometry_build(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
+                                          R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), min_weight, hip.ptr(ws),
+                                          ws.numel(), None, hip.ptr(live), hip.stream()))
+        count = int(live)
+        buf = torch.zeros(lib.tgtc_geometry_cache_bytes(R, count), dtype=torch.uint8, device=dev)   # padding bytes: 0 in the file
+        hip.check(lib.tgtc_geometry_pack(hip.ptr(ws), R, n_coarse, n_fine, min_weight, count, hip.ptr(buf), buf.numel(),
+                                         hip.stream()))
+        return GeometryCache(buf, R, n_coarse + n_fine, count, min_weight, key, n_coarse, n_fine)
+
+    def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None):
+        """The rays of `cache` under K latent sets: zs float [K,R,32] -> dict rgb [K,R,3], t [R], live (the cache's count, a
+        host int).  One launch of the compact indexed style kernel over the cached list and one compositing launch; the
+        bits of `render_latents(..., min_weight=cache.min_weight)`.  rays_o / rays_d must be the rays the cache was built
+        from (it stores depths, not positions).  ValueError before any launch if R, a given n_coarse + n_fine or a given
+        `key` does not match the cache."""
+        hip.require_gpu(rays_o, rays_d, zs, cache.buffer)
+        lib = hip.load()
+        if self.style is None:
+            raise ValueError("restyle needs a style pair")
+        R = rays_o.shape[0]
+        if R != cache.R:
+            raise ValueError("restyle: %d rays, the cache holds %d" % (R, cache.R))
+        if (n_coarse is not None or n_fine is not None) and (n_coarse, n_fine) != (cache.n_coarse, cache.n_fine):
+            raise ValueError("restyle: %s + %s samples per ray, the cache was built with %s + %s"
+                             % (n_coarse, n_fine, cache.n_coarse, cache.n_fine))
+        if key is not None and key != cache.key:
+            raise ValueError("restyle: the cache was built under another key")
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        dev = rays_o.device
+        zs = zs.to(torch.float32).contiguous()
+        if zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
+            raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
+        K = zs.shape[0]
+        need = lib.tgtc_restyle_workspace_bytes(cache.count, K)
+        if self._ws_restyle is None or self._ws_restyle.numel() < need or self._ws_restyle.device != dev:
+            self._ws_restyle = None
+            self._ws_restyle = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        ws = self._ws_restyle
+        rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
+        t = torch.empty(R, device=dev, dtype=torch.float32)
+        hip.check(lib.tgtc_restyle_rays(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
+                                        hip.ptr(zs), K, R, cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer),
+                                        cache.buffer.numel(), cache.count, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t),
+                                        hip.stream()))
+        return {"rgb": rgb, "t": t, "live": cache.count}
 
 
 # =====================================================================================================
@@ -341,13 +474,48 @@ def _styled_batch(b, args, ds, samp_func, model_forward, style_forward, concat_s
     return rgb_f, t_f
 
 
-def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None):
+def _geometry_key(ds, args, renderer, fid, p0, p1, min_weight, tag):
+    """What the geometry of pixels [p0, p1) of validation frame `fid` depends on, as one hex digest: pose, intrinsics, frame
+    size, pixel range, sample counts, near / far, the frame's jitter seed, the NeRF precisions, min_weight and the caller's
+    tag (train_tgtcs passes the NeRF checkpoint step)."""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(np.ascontiguousarray(ds.cps_valid[fid], np.float64).tobytes())
+    h.update(np.ascontiguousarray(np.asarray(ds.hwf, np.float64)).tobytes())
+    h.update(repr((int(ds.h), int(ds.w), int(p0), int(p1), int(args.N_samples), int(args.N_samples_fine), float(ds.near),
+                   float(ds.far), int(getattr(ds, 'jitter_seed', 0)), int(getattr(ds, 'jitter_samples', 0)), int(fid),
+                   renderer.coarse.packed().precision, renderer.fine.packed().precision, float(min_weight), tag)).encode())
+    return h.hexdigest()
+
+
+def _cached_geometry(renderer, directory, name, key, build):
+    """The GeometryCache in `directory`/`name` if it is there and carries `key`, else `build()` saved under that name."""
+    path = os.path.join(directory, name)
+    if os.path.exists(path):
+        try:
+            cache = GeometryCache.load(path, torch.device("cuda", torch.cuda.current_device()))
+            if cache.key == key:
+                return cache
+        except (ValueError, KeyError, RuntimeError, EOFError):
+            pass                        # unreadable or stale: rebuilt below
+    cache = build()
+    tmp = path + ".tmp%d" % os.getpid()
+    cache.save(tmp)
+    os.replace(tmp, path)
+    return cache
+
+
+def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None, geometry_cache=None,
+                         geometry_tag=None):
     """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
     `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
     style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
     hook (train_tgtcs.SyntheticScene): the rays this rank renders of each frame it takes part in -- its pixel range of
     every frame under rays sharding, whole frames dealt round-robin under frames sharding.
-    min_weight: RayRenderer.render_latents' (None: the style networks run on every sample)."""
+    min_weight: RayRenderer.render_latents' (None: the style networks run on every sample).
+    geometry_cache: a directory of GeometryCache files, one per (frame, pixel range of a call).  A file with a matching key is
+    loaded and the call becomes `RayRenderer.restyle`; otherwise the geometry is built, saved there and restyled.  The
+    images are those of min_weight (None counts as 0) without the cache, bit for bit."""
     ds = dataloader.dataset
     if renderer is None or not hasattr(ds, 'frame_batches'):
         raise ValueError("share_geometry needs renderer=RayRenderer(...) and a dataset with the frame_batches hook")
@@ -357,6 +525,10 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     # rays per call: K x R x nt samples stay below 2^31 and the per-sample colour of a call below 2 GiB
     per_call = max(1, min(((1 << 31) - 1) // (styles * nt), (2 << 30) // (styles * nt * 12)))
     rgbs, ts, have = [], [], 0
+    if geometry_cache is not None:
+        os.makedirs(geometry_cache, exist_ok=True)
+        min_weight = 0. if min_weight is None else float(min_weight)
+        first_pixel = ds._pixels()[0] if hasattr(ds, '_pixels') else 0
     for batch in ds.frame_batches(dataloader.batch_size):
         b = _to_device(batch, device)
         fid = int(b['frame_id'][0])
@@ -367,8 +539,20 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
             zs = torch.stack([latents_model_1(style_ids=torch.full_like(frame_ids, sid), frame_ids=frame_ids,
                                               type=args.dataset_type) for sid in range(styles)])
             jitter = b['jitter'][sl] if 'jitter' in b else torch.rand(frame_ids.shape[0], args.N_samples, device=device)
-            out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine, near=ds.near,
-                                          far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight)
+            if geometry_cache is not None:
+                if 'jitter' not in b:
+                    raise ValueError("geometry_cache needs a dataset that delivers its jitter per ray (a cached geometry "
+                                     "fixes the sample positions; a fresh draw per call would not be reproduced)")
+                p0, p1 = first_pixel + have + sl.start, first_pixel + have + sl.stop
+                key = _geometry_key(ds, args, renderer, fid, p0, p1, min_weight, geometry_tag)
+                ro, rd = b['rays_o'][sl], b['rays_d'][sl]
+                cache = _cached_geometry(renderer, geometry_cache, 'geometry_%05d_%09d_%09d.pt' % (fid, p0, p1), key,
+                                         lambda: renderer.build_geometry(ro, rd, args.N_samples, args.N_samples_fine, near=ds.near,
+                                                                         far=ds.far, jitter=jitter, min_weight=min_weight, key=key))
+                out = renderer.restyle(cache, ro, rd, zs, key=key, n_coarse=args.N_samples, n_fine=args.N_samples_fine)
+            else:
+                out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine,
+                                              near=ds.near, far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight)
             rgbs.append(out["rgb"].detach()), ts.append(out["t"].detach())
         have += R
         if have == res:           # a frame (this rank's part of it) is complete
@@ -385,21 +569,27 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
 
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
                  device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
-                 share_geometry=False, min_weight=None):
+                 share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
     Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
     share_geometry=True (not in the reference): all styles of a frame in one multi-latent call, see _render_style_shared.
     min_weight (not in the reference; needs `renderer`): the style networks only on the fine samples whose compositing
-    weight exceeds it, see RayRenderer.render_latents; None runs them on every sample."""
+    weight exceeds it, see RayRenderer.render_latents; None runs them on every sample.
+    geometry_cache (share_geometry only): a directory in which the ray-only half of every call is kept and reused, see
+    _render_style_shared; geometry_tag: a string that goes into the cache keys (what the driver cannot see, e.g. the NeRF
+    checkpoint step)."""
     _require_fine(args)
+    if geometry_cache is not None and not share_geometry:
+        raise ValueError("geometry_cache needs share_geometry=True (the cache belongs to the walk by frames)")
     latents_model_1.sigma_scale = sigma_scale
     if sv_path is not None:
         os.makedirs(sv_path, exist_ok=True)
     ds = dataloader.dataset
     ds.mode = 'valid_style'
     if share_geometry:
-        return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight)
+        return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight,
+                                    geometry_cache=geometry_cache, geometry_tag=geometry_tag)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0

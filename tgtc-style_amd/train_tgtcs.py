@@ -189,6 +189,7 @@ def train(args):
     style_model = models.StyleMLP_Wild_multilayers(args).to(device)
     global_step = 0
     step = None if args.no_reload else checkpoints.load_nerf(sv_path, model, model_fine)           # train_tgtcs.py:60-72
+    nerf_step = -1 if step is None else int(step)      # part of the --geometry_cache keys (-1: the seeded synthetic weights)
     if step is not None:
         global_step = step
     elif args.synthetic:
@@ -271,6 +272,7 @@ def train(args):
             model.set_enable_style(True), model_fine.set_enable_style(True)
             dataset.mode = 'valid_style'
             rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, share_geometry=args.share_geometry,
+                                   geometry_cache=args.geometry_cache or None, geometry_tag="nerf_step=%d" % nerf_step,
                                    **common, **styled)
             print('Done, saving to', out)
             return out
@@ -301,6 +303,9 @@ def _finish_distributed():
 
 def main(argv=None):
     args = cfg.parse_args(argv)
+    if args.geometry_cache and not args.share_geometry:
+        raise SystemExit("train_tgtcs: --geometry_cache needs --share_geometry (the cache is kept per frame, for all styles "
+                         "of the frame; add --share_geometry or drop --geometry_cache)")
     if args.expname is None:
         raise SystemExit("train_tgtcs: --expname (or --config) is required")
     try:
