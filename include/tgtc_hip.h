@@ -94,6 +94,16 @@ int tgtc_nerf_mlp_forward(const tgtc_net* net, const float* pts_enc, const float
 int tgtc_nerf_forward_rays(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts,
                            int64_t R, int N, float* rgb, float* sigma, void* stream);
 
+/* The same per-sample arithmetic over a device-side LIST of samples (the colour phase of the two-phase fine pass below):
+ * live uint32 [*n_live] ascending sample indices s = r x N + i, each < R x N; n_live a DEVICE pointer to one uint32 (the host
+ * never learns the count: the grid is one workgroup per CU and every workgroup reads it).  rgb[s] is written for the listed
+ * samples only -- the bits tgtc_nerf_forward_rays gives that sample -- and nothing else of rgb is touched; no density is
+ * written.  *n_live == 0 reads nothing of `live` (which must still be a valid pointer).
+ * Built for TGTC_PREC_FP16_FP6 handles only (one more instance of the two-tile persistent kernel, csrc/mlp_nerf_mx2.hip):
+ * any other precision, or R x N >= 2^31 -> TGTC_ERR_UNSUPPORTED.  Null pointers, R < 0, N < 1 -> TGTC_ERR_ARG; R == 0 -> TGTC_OK. */
+int tgtc_nerf_forward_list(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts,
+                           int64_t R, int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream);
+
 /* ------------------------------------------------------------------ a6: alpha compositing
  * utils.py:354-386 alpha_composition with sigma_noise_std=0, white_bkgd=False.  weights may be NULL. */
 int tgtc_composite(const float* rgb, const float* sigma, const float* ts, int64_t R, int N,
@@ -149,6 +159,39 @@ int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const d
                            int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter, int path,
                            void* workspace, size_t workspace_bytes,
                            float* rgb_fine, float* t_fine, float* rgb_coarse, float* t_coarse, void* stream);
+
+/* ------------------------------------------------------------------ two-phase fine pass of the plain chain
+ * A fine sample with sigma <= 0 has alpha = 1 - exp(-relu(sigma) x delta) = 0 exactly, weight +0, and leaves the pixel sum
+ * unchanged (acc + 0 x c), so its colour head is work the image does not need.  Inside TGTC_PATH_CHAIN, for a fine handle
+ * in TGTC_PREC_FP16_FP6, the fine pass can therefore run as: the density-only launch of the fine network over all
+ * R x (n_coarse + n_fine) samples; the compaction of the samples with sigma > 0 into an ascending device-side list; a
+ * zero-fill of the colour plane; tgtc_nerf_forward_list over that list; the dense compositing kernel, unchanged.  The list
+ * and the compaction scratch live in workspace planes that are dead by then: tgtc_render_workspace_bytes is what it was.
+ * tgtc_render_path and the TGTC_PATH_* values have no part in it.
+ * Images: the same BITS as the dense fine pass for finite network outputs.  The one accepted difference: a sample with
+ *   sigma <= 0 whose colour is not finite contributed 0 x NaN = NaN to the dense sum and contributes +0 now.
+ * Cost: with live share L, f the full fine launch and s the density-only one, s + L x f + ~0.5 ms instead of f: a gain
+ *   below L* = 1 - s / f and a loss above, hence a policy, held by the FINE HANDLE:
+ *   TGTC_CULL_AUTO (default)  cull iff the live share of the last chain render with this fine handle THAT HAS LANDED is
+ *                             below the library's threshold (L* less a margin); unknown share: dense.
+ *   TGTC_CULL_OFF             always dense (and no statistic is taken).
+ *   TGTC_CULL_ON              always two-phase.
+ *   Every mode takes the dense pass where the list does not fit the dead planes (6 x R x n_coarse floats <
+ *   R x (n_coarse + n_fine) x 4 + 8192 bytes), where R x (n_coarse + n_fine) >= 2^31, or for other precisions.
+ * Statistic: the handle owns one pinned 8-byte host word.  Every chain render with it as the fine handle (AUTO and ON; in
+ *   dense mode at the price of one run of the compaction's count kernel over sigma_f) ends with an asynchronous copy of
+ *   (live count, R x (n_coarse + n_fine)) into it (none where the dead planes are smaller than the 8192-byte scratch).  AUTO reads the word without waiting for the device: a pipeline that
+ *   never synchronises stays dense until a value lands.  Only the time depends on it, never a pixel.
+ * tgtc_net_set_cull: TGTC_ERR_ARG for a bad mode or a handle that is not a NeRF handle.
+ * tgtc_net_live_fraction: the share that has landed, or -1 while none has (and for NULL / style handles).
+ * tgtc_net_culled_renders: how many chain renders with this fine handle took the two-phase pass (-1 for NULL / style handles).
+ * Renders that share one fine handle from several host threads must not race on these calls. */
+#define TGTC_CULL_AUTO 0
+#define TGTC_CULL_OFF 1
+#define TGTC_CULL_ON 2
+int tgtc_net_set_cull(tgtc_net* net, int mode);
+float tgtc_net_live_fraction(const tgtc_net* net);
+long long tgtc_net_culled_renders(const tgtc_net* net);
 
 /* ------------------------------------------------------------------ a8: latent table
  * models.py:490-506 StyleLatents_variational.forward.  latents float [S,F,D] device, mu float [S,D] device,

@@ -296,6 +296,17 @@ int nerf_forward_rays_impl(const tgtc_net* net, const double* rays_o, const doub
     return rgb ? dispatch_nerf<IN_RAYS, true>(net, a, st) : dispatch_nerf<IN_RAYS, false>(net, a, st);
 }
 
+// rgb[live[i]] for the *n_live samples of a device-side list (the caller has checked the precision and R x N < 2^31)
+int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                           const uint32_t* live, const uint32_t* n_live, float* rgb, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.rgb = rgb;
+    a.live = live, a.n_live = n_live;
+    a.bias = net->dev;
+    a.stream = net->dev + net->bias_bytes;
+    return nerf_mx_launch(IN_LIST, true, a, st);
+}
+
 }  // namespace tgtc
 
 using namespace tgtc;
@@ -341,6 +352,16 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     }
     tgtc_net* net = new tgtc_net();
     net->kind = 0, net->precision = precision;
+    {
+        void* word = nullptr;   // the pinned word of the live statistic (render.hip, fine_pass)
+        hipError_t eh = hipHostMalloc(&word, sizeof(uint64_t), hipHostMallocDefault);
+        if (eh != hipSuccess) {
+            delete net;
+            return fail(TGTC_ERR_HIP, "nerf_create: hipHostMalloc: %s", hipGetErrorString(eh));
+        }
+        *static_cast<uint64_t*>(word) = 0;
+        net->cull = new tgtc_cull_state{TGTC_CULL_AUTO, static_cast<volatile uint64_t*>(word), 0, 0};
+    }
     net->bias_bytes = kNerfBiasBytes;
     net->stream_bytes = stream.size();
     net->n_frags = n_frags;
@@ -349,6 +370,8 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     size_t total = net->bias_bytes + net->stream_bytes + kRingBytes;
     hipError_t e = hipMalloc((void**)&net->dev, total);
     if (e != hipSuccess) {
+        (void)hipHostFree(const_cast<uint64_t*>(net->cull->landed));
+        delete net->cull;
         delete net;
         return fail(TGTC_ERR_HIP, "nerf_create: hipMalloc(%zu): %s", total, hipGetErrorString(e));
     }
@@ -358,6 +381,8 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     e = hipMemcpy(net->dev, host.data(), total, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(net->dev);
+        (void)hipHostFree(const_cast<uint64_t*>(net->cull->landed));
+        delete net->cull;
         delete net;
         return fail(TGTC_ERR_HIP, "nerf_create: hipMemcpy: %s", hipGetErrorString(e));
     }
@@ -367,13 +392,34 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
 
 extern "C" int tgtc_net_destroy(tgtc_net* net) {
     if (!net) return TGTC_OK;
-    hipError_t e = net->dev ? hipFree(net->dev) : hipSuccess;
+    hipError_t e = net->dev ? hipFree(net->dev) : hipSuccess;   // (waits for the device: no copy into the pinned word is left)
+    if (net->cull) {
+        (void)hipHostFree(const_cast<uint64_t*>(net->cull->landed));
+        delete net->cull;
+    }
     delete net;
     if (e != hipSuccess) return fail(TGTC_ERR_HIP, "net_destroy: hipFree: %s", hipGetErrorString(e));
     return TGTC_OK;
 }
 
 extern "C" int tgtc_net_precision(const tgtc_net* net) { return net ? net->precision : TGTC_ERR_ARG; }
+
+extern "C" int tgtc_net_set_cull(tgtc_net* net, int mode) {
+    TGTC_REQUIRE(net && net->kind == 0 && net->cull, "net_set_cull: not a NeRF handle");
+    TGTC_REQUIRE(mode == TGTC_CULL_AUTO || mode == TGTC_CULL_OFF || mode == TGTC_CULL_ON, "net_set_cull: bad mode %d", mode);
+    net->cull->mode = mode;
+    return TGTC_OK;
+}
+
+extern "C" float tgtc_net_live_fraction(const tgtc_net* net) {
+    if (!net || !net->cull) return -1.0f;
+    const uint64_t word = *net->cull->landed;   // one aligned 8-byte read: never half of a copy
+    const uint32_t live = (uint32_t)word, total = (uint32_t)(word >> 32);
+    if (total == 0 || live > total) return -1.0f;
+    return (float)((double)live / (double)total);
+}
+
+extern "C" long long tgtc_net_culled_renders(const tgtc_net* net) { return net && net->cull ? net->cull->culled : -1; }
 
 extern "C" int tgtc_nerf_forward(const tgtc_net* net, const double* pts, const double* dirs, int64_t M, float* rgb,
                                  float* sigma, float* base_remap, float* pts_enc, float* dirs_enc, void* stream) {
@@ -402,5 +448,17 @@ extern "C" int tgtc_nerf_forward_rays(const tgtc_net* net, const double* rays_o,
     if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && ts && (rgb || sigma), "nerf_forward_rays: null input");
     return nerf_forward_rays_impl(net, rays_o, rays_d, ts, R, N, rgb, sigma, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_forward_list(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts,
+                                      int64_t R, int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_forward_list: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && live && n_live && rgb, "nerf_forward_list: null pointer");
+    if (net->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list: built for fp16+fp6 handles only (got precision %d)", net->precision);
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list: R x N >= 2^31 (chunk the rays)");
+    return nerf_forward_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, as_stream(stream));
 }
 #endif  // TGTC_TU_FP16_ONLY

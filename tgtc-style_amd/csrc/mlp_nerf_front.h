@@ -5,7 +5,9 @@
 
 namespace tgtc {
 
-enum InMode { IN_RAYS = 0, IN_PTS = 1, IN_ENC = 2 };
+// IN_LIST: IN_RAYS through a list -- slot i of the launch is sample s = live[i] of the [R, N] grid (ray s / N, depth ts[s]);
+// slots at or beyond *n_live repeat the last listed sample with their stores masked
+enum InMode { IN_RAYS = 0, IN_PTS = 1, IN_ENC = 2, IN_LIST = 3 };
 
 struct NerfArgs {
     const char* bias;    // device: padded bias table
@@ -26,19 +28,28 @@ struct NerfArgs {
     float* remap;
     float* out_pts_enc;
     float* out_dirs_enc;
+    // IN_LIST (behind the rest: the other modes' argument offsets stay where they were)
+    const unsigned* live;    // ascending sample indices, each < M
+    const unsigned* n_live;  // device scalar, the list's length
 };
 
 // Ordinary global loads of a wave's NCT x 16 samples.  Must run BEFORE any LDS-DMA is issued: once a
 // global_load_lds is in flight hipcc drains vmcnt(0) -- the whole prefetch -- at the first use of a loaded value.
+// IN_LIST: s_wave counts list slots and n_live (> 0) is the list's length as the kernel read it; sidx is the sample the
+// slot stands for (a clamped slot's too: the caller masks stores by the slot, not by sidx).
 template <int NCT, int IN_MODE>
 __device__ __forceinline__ void nerf_load_samples(const NerfArgs& a, long long s_wave, int n, double (&pos)[NCT][3],
-                                                  double (&dir)[NCT][3], long long (&sidx)[NCT]) {
+                                                  double (&dir)[NCT][3], long long (&sidx)[NCT], unsigned n_live = 0) {
 #pragma unroll
     for (int c = 0; c < NCT; ++c) {
         long long s = s_wave + c * 16 + n;
+        if constexpr (IN_MODE == IN_LIST) {
+            const unsigned i = (unsigned long long)s < n_live ? (unsigned)s : n_live - 1;   // tail: the last listed sample again
+            s = a.live[i];
+        }
         sidx[c] = s;
         if (s >= a.M) s = a.M - 1;  // tail: duplicate the last sample, stores are masked
-        if constexpr (IN_MODE == IN_RAYS) {
+        if constexpr (IN_MODE == IN_RAYS || IN_MODE == IN_LIST) {
             const long long r = (unsigned)s / (unsigned)a.N;  // M < 2^31 is checked at launch
             const double t = (double)a.ts[s];
 #pragma unroll
@@ -111,7 +122,7 @@ __device__ __forceinline__ void nerf_encode_dir_late(const NerfArgs& a, long lon
         load_encoded_dir<SPLIT>(a.dirs_enc + s * 27, g, de_h, de_l);
     } else {
         double d[3];
-        const double* src = IN_MODE == IN_RAYS ? a.rays_d + ((unsigned)s / (unsigned)a.N) * 3 : a.dirs + s * 3;
+        const double* src = (IN_MODE == IN_RAYS || IN_MODE == IN_LIST) ? a.rays_d + ((unsigned)s / (unsigned)a.N) * 3 : a.dirs + s * 3;
 #pragma unroll
         for (int k = 0; k < 3; ++k) d[k] = src[k];
         encode_dir<SPLIT, SPLIT>(d, g, de_h, de_l, (a.out_dirs_enc && sidx < a.M) ? a.out_dirs_enc + sidx * 27 : nullptr);

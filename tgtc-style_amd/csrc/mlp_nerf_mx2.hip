@@ -23,9 +23,17 @@ using CfgMx2 = MlpCfg<4, 2, false, 4>;
 #endif
 
 // FULL = false: the trunk + sigma head alone (the coarse pass of a render whose coarse network is fp16mx), rays in, densities out
+// IN_LIST (the colour phase of the two-phase fine pass, render.hip): pass p owns list slots [128 p, 128 p + 128); the number
+// of passes follows from *n_live read HERE (the host's n_pass is ignored, the grid is the CU count), a workgroup without
+// a pass still runs the ring prologue and the final wait; only rgb is stored, scattered to rgb[live[slot]].
 template <int IN_MODE, bool FULL>
 __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long n_pass) {
     using C = CfgMx2;
+    unsigned n_live = 0;   // IN_LIST only; a scalar load, issued before any LDS-DMA
+    if constexpr (IN_MODE == IN_LIST) {
+        n_live = __builtin_amdgcn_readfirstlane(*a.n_live);
+        n_pass = ((long long)n_live + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;
+    }
     constexpr int NUNITS = nerf_mx_units(FULL);
     using Reader = MxReader<C, SingleStreamMap<NUNITS>, kNerfMxTable, true>;
     // the stream's ring: 128 KiB in chunks of kMx2ChunkBytes (the generator's `chunk`), every wave moves 1/4 of a chunk
@@ -74,7 +82,8 @@ __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long 
                 pe_h[0][c] = pe_h[1][c] = pe_l[0][c] = pe_l[1][c] = de_h[0][c] = de_l[0][c] =
                     half8{(_Float16)(float)(pos[c][0] + pos[c][1] + pos[c][2] + dir[c][0] + dir[c][1] + dir[c][2])};
 #else
-            nerf_load_samples<2, IN_MODE>(a, s_wave, n, pos, dir, sidx);
+            if constexpr (IN_MODE == IN_LIST) nerf_load_samples<2, IN_MODE>(a, s_wave, n, pos, dir, sidx, n_live);
+            else nerf_load_samples<2, IN_MODE>(a, s_wave, n, pos, dir, sidx);
             if constexpr (IN_MODE == IN_ENC) nerf_load_encoded<2, true, FULL>(a, sidx, g, pe_h, pe_l, de_h, de_l);
             else nerf_encode<2, true, FULL>(a, pos, dir, sidx, g, pe_h, pe_l, de_h, de_l);
 #endif
@@ -97,6 +106,18 @@ __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long 
         if (lane < 16 && !(TGTC_MX2_ABL & 2)) {   // (2: timing experiment without the output stores)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
+                if constexpr (IN_MODE == IN_LIST) {
+                    // the slot's sample is read again here: nothing but scalars lives across the stream
+                    const unsigned long long slot = (unsigned long long)(s_wave + c * 16 + lane);
+                    if (slot < n_live) {
+                        const unsigned s = a.live[slot];
+                        if (s < a.M) {   // (a list that keeps its promise never fails this)
+#pragma unroll
+                            for (int r = 0; r < 3; ++r) a.rgb[(size_t)s * 3 + r] = 1.0f / (1.0f + expf(-rgb[c][r]));   // models.py:111
+                        }
+                    }
+                    continue;
+                }
                 const long long s = s_wave + c * 16 + lane;
                 if (s < a.M) {
                     if (a.sigma) a.sigma[s] = sigma[c];
@@ -125,6 +146,8 @@ int nerf_mx2_launch(int in_mode, bool full, const NerfArgs& a, hipStream_t st) {
         case IN_RAYS * 2 + 1: nerf_mx2_kernel<IN_RAYS, true><<<nwg, block, 0, st>>>(a, n_pass); break;
         case IN_PTS * 2 + 1: nerf_mx2_kernel<IN_PTS, true><<<nwg, block, 0, st>>>(a, n_pass); break;
         case IN_ENC * 2 + 1: nerf_mx2_kernel<IN_ENC, true><<<nwg, block, 0, st>>>(a, n_pass); break;
+        // the list's length is on the device: one workgroup per CU (never more than the dense plane has passes), each reads it
+        case IN_LIST * 2 + 1: nerf_mx2_kernel<IN_LIST, true><<<nwg, block, 0, st>>>(a, 0); break;
         default: return fail(TGTC_ERR_UNSUPPORTED, "nerf (fp16+fp6, two tiles): no kernel for input mode %d, full %d", in_mode, (int)full);
     }
     TGTC_LAUNCH_CHECK();

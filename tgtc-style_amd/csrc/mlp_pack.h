@@ -157,6 +157,16 @@ inline PackedNet pack_layers(const std::vector<LayerSpec>& layers, bool split) {
 
 }  // namespace tgtc
 
+// What a NeRF handle keeps about the two-phase fine pass of the plain render (render.hip, tgtc_net_set_cull): the mode, one
+// pinned host word that every chain render with this handle as its fine network ends in an asynchronous copy of
+// (live count, R x (n_coarse + n_fine)) into, and how many of those renders took which branch.  Reached through a
+// pointer: the render entry points take the handle as const.
+struct tgtc_cull_state {
+    int mode;                        // TGTC_CULL_*
+    volatile uint64_t* landed;       // pinned: low word the live count, high word the sample count; 0 = nothing landed yet
+    long long culled, dense;         // chain renders that took the two-phase fine pass / the dense one
+};
+
 // The opaque handle of the C ABI.
 struct tgtc_net {
     int kind;        // 0 = NeRF (StyleNerf), 1 = style pair (concat MLP + style MLP)
@@ -171,4 +181,5 @@ struct tgtc_net {
     size_t stash_off;  // per-workgroup scratch slabs of the fused stylised kernel
     size_t stash2_off; // a second region of the same size (base_remap across the latents of mlp_style_multi.hip)
     int n_wg;          // persistent grid size (= CUs)
+    tgtc_cull_state* cull;  // NeRF handles only (tgtc_nerf_create)
 };

@@ -377,6 +377,44 @@ int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* l
 
 static_assert((kCompactCountWord + kCompactParts) * sizeof(uint32_t) <= kSparseScratchBytes, "counts must fit the scratch");
 
+// The live statistic of a plain chain render (render.hip): scratch words 2 and 3 = (number of samples with w > min_weight, M),
+// the pair the render copies to the fine handle's pinned word.  launch_count_live is pass 1 of the compaction alone (a dense
+// render has no use for the list); launch_live_stat sums the counts either form of pass 1 left behind.
+constexpr int kCompactStatWord = 2;
+static_assert(kCompactStatWord + 2 <= kCompactCountWord, "the statistic lies in front of the counts");
+
+__global__ void __launch_bounds__(kCompactBlock) compact_stat_kernel(const unsigned* __restrict__ counts, unsigned M,
+                                                                     unsigned* __restrict__ stat) {
+    __shared__ unsigned red[kCompactBlock / 64];
+    unsigned all = 0;
+    for (unsigned p = threadIdx.x; p < kCompactParts; p += kCompactBlock) all += counts[p];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) all += __shfl_xor(all, d);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = all;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned tot = 0;
+#pragma unroll
+        for (int i = 0; i < kCompactBlock / 64; ++i) tot += red[i];
+        stat[0] = tot, stat[1] = M;
+    }
+}
+
+int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scratch, hipStream_t st) {
+    const int64_t per = (M + kCompactParts - 1) / kCompactParts;
+    const unsigned span = (unsigned)((per + kCompactBlock - 1) / kCompactBlock * kCompactBlock);
+    compact_count_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st) {
+    compact_stat_kernel<<<1, kCompactBlock, 0, st>>>(scratch + kCompactCountWord, (unsigned)M, scratch + kCompactStatWord);
+    TGTC_LAUNCH_CHECK();
+    *stat = scratch + kCompactStatWord;
+    return TGTC_OK;
+}
+
 // rgb[k, s] for the samples of the list; the caller has zero-filled rgb.  n_live is read on the device: the grid is sized
 // for the dense plane and workgroups without a tile leave at once.
 int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,

@@ -28,6 +28,10 @@ int styled_forward_rays_sparse_impl(const tgtc_net* nerf, const tgtc_net* style,
                                     const uint32_t* n_live, float* rgb, hipStream_t st);
 int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
                         hipStream_t st);
+int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scratch, hipStream_t st);
+int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st);
+int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                           const uint32_t* live, const uint32_t* n_live, float* rgb, hipStream_t st);
 
 int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
                              const float* z, int K, int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count,
@@ -163,6 +167,76 @@ extern "C" int tgtc_render_path(int request, int prec_coarse, int prec_fine, int
     return request;
 }
 
+// ---- the two-phase fine pass of the plain chain
+// A fine sample with sigma <= 0 has alpha = 1 - exp(-relu(sigma) delta) = 0 exactly, weight 0 x T = +0, and enters the pixel
+// as acc + 0 x c: for finite colours the image does not need its colour head.  With the live share L of the samples, f the
+// full fine launch and s the density-only one, "densities, compaction, colours of the listed samples into a zero-filled
+// plane" costs s + L f + ~0.5 ms against f, a gain while L < L* = 1 - s / f.
+// kCullLiveThreshold = L* less a margin, both measured on the MI355X (tools/time_plain_cull.py --step0,
+// profiles/plain_cull_timing.json): on the fine depths of a real 400 x 400 render at 128 + 64, f = 53.10 ms and
+// s = 43.75 ms, L* = 0.176.  The margin is the whole spread of the live
+// share over the benchmark's orbit (spiral_pose 0 .. 119: 0.098 .. 0.127, so 0.029; consecutive poses differ by 0.0013 at
+// most), which lets the statistic come from ANY frame of the orbit, plus the fixed cost of the extra launches (0.4 ms of
+// f, 0.007): 0.176 - 0.029 - 0.007 = 0.14.
+constexpr float kCullLiveThreshold = 0.14f;
+
+// AUTO: cull iff the last share that LANDED in the handle's pinned word is below the threshold; nothing landed yet, or a
+// word that cannot be a (live, total) pair: dense.  The read never waits for the device, and both branches give the same
+// bits, so what a caller cannot know -- whether its previous render has finished -- only ever changes the time.
+static bool cull_wanted(const tgtc_cull_state* c) {
+    if (c->mode != TGTC_CULL_AUTO) return c->mode == TGTC_CULL_ON;
+    const uint64_t word = *c->landed;
+    const uint32_t live = (uint32_t)word, total = (uint32_t)(word >> 32);
+    return total != 0 && live <= total && (double)live < (double)kCullLiveThreshold * (double)total;
+}
+
+// The fine pass and the fine image of the plain chain.  The list and the compaction's scratch live in the planes that are
+// dead once the fine depths exist (ts_c, sigma_c, rgb_c, w_c: contiguous, and the coarse image has been composited): the
+// workspace does not grow.  Where they do not fit, or the samples cannot be indexed by 32 bits, the pass is dense.
+static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int nt,
+                     const RenderWorkspace& ws, float* rgb_fine, float* t_fine, hipStream_t st) {
+    const int64_t M = R * (int64_t)nt;
+    char* const dead = reinterpret_cast<char*>(ws.ts_c);
+    const size_t dead_bytes = (size_t)(reinterpret_cast<char*>(ws.ts_f) - dead);
+    tgtc_cull_state* const c = fine->cull;
+    const bool listable = c && fine->precision == TGTC_PREC_FP16_FP6 && M < ((int64_t)1 << 31);
+    const bool cull = listable && dead_bytes >= (size_t)M * 4 + kSparseScratchBytes && cull_wanted(c);
+    uint32_t* scratch = nullptr;
+    int rc;
+    if (cull) {
+        uint32_t* const live = reinterpret_cast<uint32_t*>(dead);
+        scratch = reinterpret_cast<uint32_t*>(dead + (size_t)M * 4);
+        rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
+        if (rc) return rc;
+        rc = launch_compact_live(ws.sigma_f, M, 0.0f, live, scratch, nullptr, st);
+        if (rc) return rc;
+        TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)M * 3 * sizeof(float), st));   // unlisted samples keep colour +0
+        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, st);
+        if (rc) return rc;
+        ++c->culled;
+    } else {
+        rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ws.rgb_f, ws.sigma_f, st);
+        if (rc) return rc;
+        // the statistic alone: one run of the compaction's count kernel over sigma_f
+        if (listable && c->mode != TGTC_CULL_OFF && dead_bytes >= kSparseScratchBytes) {
+            scratch = reinterpret_cast<uint32_t*>(dead);
+            rc = launch_count_live(ws.sigma_f, M, 0.0f, scratch, st);
+            if (rc) return rc;
+        }
+        if (c) ++c->dense;
+    }
+    rc = launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st);
+    if (rc) return rc;
+    if (scratch) {
+        // (live count, M) -> the handle's pinned word, asynchronously; the next render's AUTO reads whatever has landed
+        const uint32_t* stat = nullptr;
+        rc = launch_live_stat(scratch, M, &stat, st);
+        if (rc) return rc;
+        TGTC_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(c->landed), stat, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    return TGTC_OK;
+}
+
 // The plain render: ONE launch of the fused ray kernel (render_fused.hip; the workspace is not touched) or the chain of
 // per-sample kernels through the workspace, as `path` resolves.
 extern "C" int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
@@ -195,9 +269,8 @@ extern "C" int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fi
     if (rc) return rc;
     rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
     if (rc) return rc;
-    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, n_coarse + n_fine, ws.rgb_f, ws.sigma_f, st);
-    if (rc) return rc;
-    return launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, n_coarse + n_fine, rgb_fine, t_fine, nullptr, st);
+    // fine pass + fine image: dense, or densities first and the colour head on the live samples only (fine_pass above)
+    return fine_pass(fine, rays_o, rays_d, R, n_coarse + n_fine, ws, rgb_fine, t_fine, st);
 }
 
 // rendering.py:118-178 (render_style): ONE launch of the stylised ray kernel (render_styled_fused.hip; the workspace is not

@@ -22,6 +22,10 @@ PATH_AUTO = 0         # tgtc_render_path: the library's fastest path for the ren
 PATH_RAY_KERNEL = 1   # one launch of the persistent ray kernel, no workspace
 PATH_CHAIN = 2        # per-sample kernels through the workspace (the split path for coarse fp16x3 + fine fp16mx)
 
+CULL_AUTO = 0         # tgtc_net_set_cull: two-phase fine pass iff the last landed live share is below the library's threshold
+CULL_OFF = 1          # always the dense fine pass
+CULL_ON = 2           # always densities first, the colour head on the live samples only
+
 _lib = None
 
 c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -48,6 +52,10 @@ _SIGNATURES = {
     "tgtc_nerf_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_forward_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
+    "tgtc_nerf_forward_list": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_net_set_cull": [c_void_p, c_int],
+    "tgtc_net_live_fraction": [c_void_p],
+    "tgtc_net_culled_renders": [c_void_p],
     "tgtc_composite": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_train": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
@@ -62,7 +70,7 @@ _SIGNATURES = {
                              c_void_p, c_void_p],
     "tgtc_latents_backward": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p],
 }
-_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_render_workspace_bytes": c_size_t,
+_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_float, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
              "tgtc_render_styled_multi_workspace_bytes": c_size_t,
              "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
              "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t}
@@ -179,6 +187,18 @@ class Net:
     def __init__(self, handle, precision):
         self.handle = handle
         self.precision = precision
+
+    def set_cull(self, mode):
+        """The policy of the two-phase fine pass for chain renders with this net as the fine network (CULL_*)."""
+        check(load().tgtc_net_set_cull(self.handle, mode))
+
+    def live_fraction(self):
+        """Share of fine samples with sigma > 0 in the last such render whose statistic has landed; -1.0 while unknown."""
+        return float(load().tgtc_net_live_fraction(self.handle))
+
+    def culled_renders(self):
+        """How many of those renders took the two-phase fine pass."""
+        return int(load().tgtc_net_culled_renders(self.handle))
 
     def __del__(self):
         try:

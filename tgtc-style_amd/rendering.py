@@ -85,18 +85,30 @@ class RayRenderer:
     style: optional `models.StylePair` for the stylised chain.
     """
 
-    def __init__(self, coarse, fine, style=None, fused=True):
+    _CULL = {None: hip.CULL_AUTO, False: hip.CULL_OFF, True: hip.CULL_ON}
+
+    def __init__(self, coarse, fine, style=None, fused=True, cull=None):
         """fused=True: the library's fastest path (TGTC_PATH_AUTO) -- a single persistent ray kernel where one is built, except
         for coarse fp16x3 + fine fp16mx, whose fine pass runs faster on the two-tile per-sample kernel (the split path).
         fused="single" asks for the single ray kernel and nothing else (TGTC_PATH_RAY_KERNEL).  fused=False forces the chain
         of per-sample kernels (TGTC_PATH_CHAIN).  All three agree to rounding, the network arithmetic bit for bit
-        (tests/test_fused_gpu.py).  include/tgtc_hip.h, tgtc_render_path, holds the rule."""
+        (tests/test_fused_gpu.py).  include/tgtc_hip.h, tgtc_render_path, holds the rule.
+        cull (plain render on the chain, fine fp16mx): None leaves the two-phase fine pass to the library (TGTC_CULL_AUTO:
+        densities first and the colour head on the live samples only once the fine handle has seen a low enough live
+        share), True / False force it on / off.  The mode lives on the FINE HANDLE and is set by every plain render of
+        this renderer; the images are the same bits either way (include/tgtc_hip.h)."""
         if fused not in (True, False, "single"):
             raise ValueError("fused must be True, False or 'single'")
-        self.coarse, self.fine, self.style, self.fused = coarse, fine, style, fused
+        if cull not in self._CULL:
+            raise ValueError("cull must be None, True or False")
+        self.coarse, self.fine, self.style, self.fused, self.cull = coarse, fine, style, fused, cull
         self._ws = None
         self._ws_multi = None
         self._ws_restyle = None
+
+    def apply_cull(self):
+        """Put this renderer's `cull` on the fine handle (a host call; handles are repacked when weights change)."""
+        self.fine.packed().set_cull(self._CULL[self.cull])
 
     _REQUEST = {True: hip.PATH_AUTO, "single": hip.PATH_RAY_KERNEL, False: hip.PATH_CHAIN}
 
@@ -164,6 +176,7 @@ class RayRenderer:
         rest = (path, hip.ptr(ws), 0 if ws is None else ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(rgb_c), hip.ptr(t_c),
                    hip.stream())
         if plain:
+            self.apply_cull()
             hip.check(lib.tgtc_render_rays_plain(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o),
                                                  hip.ptr(rays_d), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
                                                  *rest))
