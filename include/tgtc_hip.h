@@ -356,6 +356,53 @@ int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, const double*
                       int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
                       void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
 
+/* ------------------------------------------------------------------ frame-constant latents folded into per-latent biases
+ * In a stylised frame the latent depends on (style, frame), not on the ray: the callers above receive K vectors copied R
+ * times.  For a latent that is constant over a call, its k-step in each of the 13 layers of the two style networks computes
+ * the same 256-vector for every sample -- a bias.  The entry points below take z float [K,32]:
+ *   tgtc_style_fold_latents writes K bias tables, each in the layout of the handle's own pair bias table (16 KiB: 16 floats
+ *     per row tile, concat layers 0..4 then style layers 0..7):
+ *       b'[l][o] = b[l][o] + sum_j Wz[l][o][j] x u_j,   u = z[k] for the concat layers, u_j = mean(z[k]) for the style layers,
+ *     from the handle's power-of-two equalised rows and biases (those its streams were packed from), accumulated in float64
+ *     over j = 0..31 and rounded once.  z[k] = 0 reproduces the handle's table bit for bit.
+ *   the folded kernels (csrc/mlp_style_sparse.hip) walk a second pair of streams the handle packs without the latent k-steps:
+ *     576 + 1096 fragments per latent instead of 656 + 1209 (10.3 % fewer MFMAs per latent), no latent operand, no z plane.
+ *     A folded layer is the unfolded layer's MFMA sequence with the latent k-step left out: with z = 0 the results are the
+ *     bits of the unfolded siblings with zs = 0.  With z != 0 they differ from the unfolded ones within the precision's error
+ *     (the fold is exact to float32 rounding; the unfolded kernels round the latent operand to fp16 or fp16 hi + lo).
+ * They are modes the caller asks for; nothing selects them.  The geometry cache holds no latents: the same cache serves
+ * tgtc_restyle_rays and tgtc_restyle_rays_folded.
+ *
+ * tgtc_style_folded_bytes(K): K x 16384; 0 for K < 1.
+ * tgtc_style_fold_latents: z float [K,32] (device) -> folded (device, at least tgtc_style_folded_bytes(K) bytes).
+ * tgtc_styled_forward_list_folded: the scattered kernel alone (the seam the parity tests use).  ts float [R,N]; folded: the K
+ *   tables; live uint32 [*n_live] ascending sample indices s = r x N + i, n_live a DEVICE pointer to one uint32; rgb float
+ *   [K,R,N,3], zero-filled by the caller: rgb[k,s] is written for the listed samples only.
+ * tgtc_render_rays_styled_sparse_folded: tgtc_render_rays_styled_sparse with z float [K,32].  Workspace: the sparse workspace
+ *   followed by one more plane, tgtc_style_folded_bytes(K) rounded up to 256 (the tables).
+ * tgtc_restyle_rays_folded: tgtc_restyle_rays with z float [K,32].  Workspace: tgtc_restyle_workspace_bytes(count, K) followed
+ *   by the same plane; count == 0 launches neither the fold nor a style kernel.
+ * Errors and conventions are those of the unfolded siblings (every argument check returns before a device is touched):
+ *   K < 1, null pointers, wrong handle kinds, differing precisions, min_weight < 0 or NaN, buffers below their size functions
+ *   -> TGTC_ERR_ARG;  K x R x N >= 2^31 or K x count >= 2^31 -> TGTC_ERR_UNSUPPORTED;  R == 0 -> TGTC_OK.  The size and range
+ *   checks come before the handles are looked at.  Both slab regions of the STYLE HANDLE are used; launches on one style handle
+ *   must not overlap. */
+size_t tgtc_style_folded_bytes(int K);
+int tgtc_style_fold_latents(const tgtc_net* style, const float* z, int K, void* folded, size_t folded_bytes, void* stream);
+int tgtc_styled_forward_list_folded(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const float* ts, const void* folded, int K, int64_t R, int N, const uint32_t* live,
+                                    const uint32_t* n_live, float* rgb, void* stream);
+size_t tgtc_render_styled_sparse_folded_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K);
+int tgtc_render_rays_styled_sparse_folded(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                          const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                          int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                          float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                          float* t_fine, uint32_t* live_count, void* stream);
+size_t tgtc_restyle_folded_workspace_bytes(int64_t count, int K);
+int tgtc_restyle_rays_folded(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                             const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
+                             int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ EXTRA = {
     "share_geometry": (None, False),   # --render_valid_style: all styles of a frame in ONE multi-latent call (HELP below)
     "cull_weight": (float, -1.0),      # stylised renders: style networks only where the compositing weight exceeds it (HELP below)
     "geometry_cache": (str, ""),       # --share_geometry: directory of cached ray geometry, reused across runs (HELP below)
+    "fold_latents": (None, False),     # --share_geometry with --cull_weight or --geometry_cache: one latent per (style, frame) (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
 }
@@ -69,6 +70,14 @@ HELP = {
                       "step, precisions and --cull_weight is restyled from it without any NeRF density pass; otherwise it "
                       "is built and saved.  The images are those of the run without the cache, bit for bit.  An unset "
                       "--cull_weight means 0 here",
+    "fold_latents": "with --render_valid_style --share_geometry and either --cull_weight >= 0 or --geometry_cache (refused "
+                    "otherwise): hand the style networks ONE latent per (style, frame) instead of a copy per ray.  The "
+                    "latent columns of the two style networks are folded into a bias table per style and the kernels run "
+                    "without the latent k-steps, so no [styles, rays, 32] latent plane is built (20 MB per style for a "
+                    "400 x 400 frame) and each style costs a tenth fewer matrix operations per live sample.  The colour "
+                    "images agree with the run without the flag to the precision's rounding (at most one 8-bit level), the "
+                    "depth images bit for bit, and a --geometry_cache directory serves both.  All rays of a call must "
+                    "belong to one frame",
 }
 
 

@@ -68,4 +68,28 @@ static_assert(kConcatFrags == 656 && kStyleFrags == 1209, "fragment counts");
 constexpr int kStylePairBiasBytes = 16384;
 static_assert((kConcatBiasFloats + kStyleBiasFloats) * 4 <= kStylePairBiasBytes, "style bias table");
 
+// ---- the same two nets with the latent k-step z(1) of every layer folded into a per-latent bias table (a latent that is
+//      constant over a launch; mlp_style_sparse.hip, FOLD): the remaining k-steps in their order, row tiles and bias offsets
+//      unchanged (style_bias0, kStyleRT)
+//   concat  L0 [pe(2)]   L1-3 [h(8)]   L4 [h(8) | pe(2)]
+//   style   L0 [remap(8) | cf(8) | pe(2)]   L1-3,5,6 [h(8)]   L4 [h(8) | pe(2)]   L7 [h(8)]
+constexpr int kConcatFoldKS[5] = {2, 8, 8, 8, 10};
+constexpr int concat_fold_frag0(int l) {
+    int f = 0;
+    for (int i = 0; i < l; ++i) f += kConcatFoldKS[i] * 16;
+    return f;
+}
+constexpr int kStyleFoldKS[8] = {18, 8, 8, 8, 10, 8, 8, 8};
+constexpr int style_fold_frag0(int l) {
+    int f = 0;
+    for (int i = 0; i < l; ++i) f += kStyleFoldKS[i] * kStyleRT[i];
+    return f;
+}
+constexpr int kConcatFoldFrags = concat_fold_frag0(5);  // 576
+constexpr int kStyleFoldFrags = style_fold_frag0(8);    // 1096
+static_assert(kConcatFoldFrags == 576 && kStyleFoldFrags == 1096, "folded fragment counts");
+// rows of the 13 layers, which are also their positions in the pair bias table: concat 256 l + o, style 1280 + 256 l + o
+constexpr int kFoldRows = 12 * 256 + 3;
+static_assert(kFoldRows == kConcatBiasFloats + style_bias0(7) + 3, "a latent row per bias table entry of a real output");
+
 }  // namespace tgtc

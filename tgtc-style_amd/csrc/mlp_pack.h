@@ -155,6 +155,24 @@ inline PackedNet pack_layers(const std::vector<LayerSpec>& layers, bool split) {
     return p;
 }
 
+// The same layers without their latent segment (SEG_VEC32), the remaining k-steps in their order: the streams of the folded
+// kernels, in which the latent's k-step is a per-latent bias (tgtc_style_fold_latents).
+inline std::vector<LayerSpec> without_latent(std::vector<LayerSpec> layers) {
+    for (LayerSpec& L : layers)
+        L.segs.erase(std::remove_if(L.segs.begin(), L.segs.end(), [](const Seg& s) { return s.kind == SEG_VEC32; }), L.segs.end());
+    return layers;
+}
+
+// The latent columns of the layers, one row of 32 floats per output row, appended to `out` layer after layer.
+inline void append_latent_columns(const std::vector<LayerSpec>& layers, std::vector<float>& out) {
+    for (const LayerSpec& L : layers)
+        for (const Seg& s : L.segs) {
+            if (s.kind != SEG_VEC32) continue;
+            for (int row = 0; row < L.out; ++row)
+                for (int j = 0; j < 32; ++j) out.push_back(L.W[(size_t)row * L.in + s.col0 + j]);
+        }
+}
+
 }  // namespace tgtc
 
 // What a NeRF handle keeps about the two-phase fine pass of the plain render (render.hip, tgtc_net_set_cull): the mode, one
@@ -181,5 +199,8 @@ struct tgtc_net {
     size_t stash_off;  // per-workgroup scratch slabs of the fused stylised kernel
     size_t stash2_off; // a second region of the same size (base_remap across the latents of mlp_style_multi.hip)
     int n_wg;          // persistent grid size (= CUs)
+    // style pair only, behind the slabs: the two streams packed without the latent k-steps and the equalised fp32 latent
+    // columns [kFoldRows, 32] of the 13 layers (tgtc_style_fold_latents and the folded kernels of mlp_style_sparse.hip)
+    size_t fold_stream_off, fold_stream2_off, fold_wz_off;
     tgtc_cull_state* cull;  // NeRF handles only (tgtc_nerf_create)
 };

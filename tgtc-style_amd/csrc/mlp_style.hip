@@ -420,6 +420,46 @@ int styled_forward_rays_impl(const tgtc_net* nerf, const tgtc_net* style, const 
     return TGTC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ latent fold
+// One block per latent: table k = the handle's pair bias table with the latent k-step of every layer added,
+//   b'[l][o] = b[l][o] + sum_j Wz[l][o][j] * u_j,   u = z_k (concat layers), u_j = mean(z_k) (style layers, rendering.py:126),
+// in float64 over j = 0..31 in order, rounded once.  Entries without an output row (the rgb head's rows 3..15, the padding)
+// are copied, so that z_k = 0 gives the handle's table bit for bit.
+constexpr int kFoldBlock = 256;
+__global__ void __launch_bounds__(kFoldBlock) fold_latents_kernel(const float* __restrict__ base, const float* __restrict__ wz,
+                                                                  const float* __restrict__ z, float* __restrict__ folded) {
+    constexpr int kTableFloats = kStylePairBiasBytes / 4;
+    const float* zk = z + (size_t)blockIdx.x * 32;
+    double u[32], sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) u[j] = (double)zk[j], sum += u[j];
+    const double mean = sum * (1.0 / 32.0);
+    float* out = folded + (size_t)blockIdx.x * kTableFloats;
+    for (int t = threadIdx.x; t < kTableFloats; t += kFoldBlock) {
+        float v = base[t];
+        if (t < kFoldRows) {
+            const float* w = wz + (size_t)t * 32;
+            double acc = (double)v;
+            if (t < kConcatBiasFloats) {
+#pragma unroll
+                for (int j = 0; j < 32; ++j) acc += (double)w[j] * u[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 32; ++j) acc += (double)w[j] * mean;
+            }
+            v = (float)acc;
+        }
+        out[t] = v;
+    }
+}
+
+int style_fold_latents_impl(const tgtc_net* style, const float* z, int K, float* folded, hipStream_t st) {
+    fold_latents_kernel<<<(unsigned)K, kFoldBlock, 0, st>>>(reinterpret_cast<const float*>(style->dev),
+                                                            reinterpret_cast<const float*>(style->dev + style->fold_wz_off), z, folded);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
 }  // namespace tgtc
 
 using namespace tgtc;
@@ -467,6 +507,18 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
     for (int i = 0; i < 8; ++i)
         if (ps.frag0[i] != style_frag0(i) || ps.bias0[i] != style_bias0(i))
             return fail(TGTC_ERR_UNSUPPORTED, "style_create: internal layout mismatch at style layer %d", i);
+    // the same equalised layers without the latent k-steps, and the latent columns they leave out (folded kernels)
+    PackedNet pcf = pack_layers(without_latent(concat_specs(concat_layers)), split);
+    PackedNet psf = pack_layers(without_latent(style_specs(style_layers)), split);
+    std::vector<float> wz;
+    append_latent_columns(concat_specs(concat_layers), wz);
+    append_latent_columns(style_specs(style_layers), wz);
+    if (pcf.n_frags != kConcatFoldFrags || psf.n_frags != kStyleFoldFrags || pcf.bias.size() != pc.bias.size() ||
+        psf.bias.size() != ps.bias.size() || (int)wz.size() != kFoldRows * 32)
+        return fail(TGTC_ERR_UNSUPPORTED, "style_create: internal layout mismatch of the folded streams");
+    for (int i = 0; i < 8; ++i)
+        if (psf.frag0[i] != style_fold_frag0(i))
+            return fail(TGTC_ERR_UNSUPPORTED, "style_create: internal layout mismatch at folded style layer %d", i);
     int n_cu = 0;
     if (const int rc = cu_count(n_cu)) return rc;
     tgtc_net* net = new tgtc_net();
@@ -480,7 +532,11 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
     net->n_wg = n_cu;  // one persistent workgroup per CU (the LDS ring allows exactly one)
     net->stash_off = (net->stream2_off + net->stream2_bytes + kChunkBytes + 255) & ~(size_t)255;
     net->stash2_off = net->stash_off + (size_t)net->n_wg * kStashBytesPerWG;
-    const size_t total = net->stash2_off + (size_t)net->n_wg * kStashBytesPerWG;
+    // behind what was there: [folded concat stream][folded style stream][a chunk of padding][latent columns]
+    net->fold_stream_off = net->stash2_off + (size_t)net->n_wg * kStashBytesPerWG;
+    net->fold_stream2_off = net->fold_stream_off + pcf.stream.size() * sizeof(half_t);
+    net->fold_wz_off = (net->fold_stream2_off + psf.stream.size() * sizeof(half_t) + kChunkBytes + 255) & ~(size_t)255;
+    const size_t total = net->fold_wz_off + wz.size() * sizeof(float);
     hipError_t e = hipMalloc((void**)&net->dev, total);
     if (e != hipSuccess) {
         delete net;
@@ -492,6 +548,13 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
     memcpy(host.data() + net->bias_bytes, pc.stream.data(), net->stream_bytes);
     memcpy(host.data() + net->stream2_off, ps.stream.data(), net->stream2_bytes);
     e = hipMemcpy(net->dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        std::vector<char> fold(total - net->fold_stream_off, 0);
+        memcpy(fold.data(), pcf.stream.data(), pcf.stream.size() * sizeof(half_t));
+        memcpy(fold.data() + (net->fold_stream2_off - net->fold_stream_off), psf.stream.data(), psf.stream.size() * sizeof(half_t));
+        memcpy(fold.data() + (net->fold_wz_off - net->fold_stream_off), wz.data(), wz.size() * sizeof(float));
+        e = hipMemcpy(net->dev + net->fold_stream_off, fold.data(), fold.size(), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         (void)hipFree(net->dev);
         delete net;
@@ -532,5 +595,17 @@ extern "C" int tgtc_styled_forward_rays(const tgtc_net* nerf, const tgtc_net* st
     if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && ts && z && rgb, "styled_forward_rays: null pointer");
     return styled_forward_rays_impl(nerf, style, rays_o, rays_d, ts, z, R, N, rgb, sigma, as_stream(stream));
+}
+
+extern "C" size_t tgtc_style_folded_bytes(int K) { return K < 1 ? 0 : (size_t)K * kStylePairBiasBytes; }
+
+extern "C" int tgtc_style_fold_latents(const tgtc_net* style, const float* z, int K, void* folded, size_t folded_bytes,
+                                       void* stream) {
+    TGTC_REQUIRE(K >= 1, "style_fold_latents: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(style && style->kind == 1, "style_fold_latents: style must be a style handle");
+    TGTC_REQUIRE(z && folded, "style_fold_latents: null pointer");
+    TGTC_REQUIRE(folded_bytes >= tgtc_style_folded_bytes(K), "style_fold_latents: %zu bytes for the tables, need %zu", folded_bytes,
+                 tgtc_style_folded_bytes(K));
+    return style_fold_latents_impl(style, z, K, static_cast<float*>(folded), as_stream(stream));
 }
 #endif  // TGTC_TU_FP16_ONLY

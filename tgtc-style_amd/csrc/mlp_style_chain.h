@@ -159,6 +159,67 @@ __device__ __forceinline__ void style_tail(WS& ws, lds_cptr bias_lane, const hal
     hidden(ic<7>{}, Xh, Xl, [&](auto, auto c_, auto h_, const float4v& acc) { emit(c_, h_, acc); });
 }
 
+// ------------------------------------------------------------------------------------------------
+// The two helpers above for a latent that is constant over the launch: the latent k-step of every layer has been added to the
+// bias table (tgtc_style_fold_latents), the streams are packed without it (kConcatFoldKS / kStyleFoldKS), and each layer is
+// the layer above with that k-step's MFMAs left out -- the remaining k-steps in the same order on the same operands.
+template <class C, int F0, int B0, class WS>
+__device__ __forceinline__ void concat_mlp_folded(WS& ws, lds_cptr bias_lane, const half8 (&pe_h)[2][C::NCT],
+                                                  const half8 (&pe_l)[2][C::NCT], half8 (&Xh)[8][C::NCT], half8 (&Xl)[8][C::NCT],
+                                                  half8 (&Yh)[8][C::NCT], half8 (&Yl)[8][C::NCT]) {
+    constexpr int NCT = C::NCT;
+    auto to_Y = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+        constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+        store_act<C, rt, decltype(h_)::value>(acc, Yh[rt / 2][c], Yl[rt / 2][c]);
+    };
+    auto to_X = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+        constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+        store_act<C, rt, decltype(h_)::value>(acc, Xh[rt / 2][c], Xl[rt / 2][c]);
+    };
+    dense_layer<C, F0 + concat_fold_frag0(0), 2, 16, B0 + 0>(ws, bias_lane, pe_h, pe_l, to_Y);
+    dense_layer<C, F0 + concat_fold_frag0(1), 8, 16, B0 + 256 * 1>(ws, bias_lane, Yh, Yl, to_X);
+    dense_layer<C, F0 + concat_fold_frag0(2), 8, 16, B0 + 256 * 2>(ws, bias_lane, Xh, Xl, to_Y);
+    dense_layer<C, F0 + concat_fold_frag0(3), 8, 16, B0 + 256 * 3>(ws, bias_lane, Yh, Yl, to_X);
+    {
+        half8 Bh[10][NCT], Bl[10][NCT];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) append<C>(Bh, Bl, k, Xh[k], Xl[k]);
+        append<C>(Bh, Bl, 8, pe_h[0], pe_l[0]);
+        append<C>(Bh, Bl, 9, pe_h[1], pe_l[1]);
+        dense_layer<C, F0 + concat_fold_frag0(4), 10, 16, B0 + 256 * 4>(ws, bias_lane, Bh, Bl, to_Y);
+    }
+}
+
+template <class C, int F0, int B0, class WS, class Emit>
+__device__ __forceinline__ void style_tail_folded(WS& ws, lds_cptr bias_lane, const half8 (&pe_h)[2][C::NCT],
+                                                  const half8 (&pe_l)[2][C::NCT], half8 (&Xh)[8][C::NCT], half8 (&Xl)[8][C::NCT],
+                                                  half8 (&Yh)[8][C::NCT], half8 (&Yl)[8][C::NCT], Emit&& emit) {
+    constexpr int NCT = C::NCT;
+    auto to_Y = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+        constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+        store_act<C, rt, decltype(h_)::value>(acc, Yh[rt / 2][c], Yl[rt / 2][c]);
+    };
+    auto to_X = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+        constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
+        store_act<C, rt, decltype(h_)::value>(acc, Xh[rt / 2][c], Xl[rt / 2][c]);
+    };
+    dense_layer<C, F0 + style_fold_frag0(1), 8, 16, B0 + style_bias0(1)>(ws, bias_lane, Xh, Xl, to_Y);
+    dense_layer<C, F0 + style_fold_frag0(2), 8, 16, B0 + style_bias0(2)>(ws, bias_lane, Yh, Yl, to_X);
+    dense_layer<C, F0 + style_fold_frag0(3), 8, 16, B0 + style_bias0(3)>(ws, bias_lane, Xh, Xl, to_Y);
+    {
+        half8 Bh[10][NCT], Bl[10][NCT];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) append<C>(Bh, Bl, k, Yh[k], Yl[k]);
+        append<C>(Bh, Bl, 8, pe_h[0], pe_l[0]);
+        append<C>(Bh, Bl, 9, pe_h[1], pe_l[1]);
+        dense_layer<C, F0 + style_fold_frag0(4), 10, 16, B0 + style_bias0(4)>(ws, bias_lane, Bh, Bl, to_X);
+    }
+    dense_layer<C, F0 + style_fold_frag0(5), 8, 16, B0 + style_bias0(5)>(ws, bias_lane, Xh, Xl, to_Y);
+    dense_layer<C, F0 + style_fold_frag0(6), 8, 16, B0 + style_bias0(6)>(ws, bias_lane, Yh, Yl, to_X);
+    dense_layer<C, F0 + style_fold_frag0(7), 8, kStyleRT[7], B0 + style_bias0(7)>(
+        ws, bias_lane, Xh, Xl, [&](auto, auto c_, auto h_, const float4v& acc) { emit(c_, h_, acc); });
+}
+
 template <bool SPLIT>
 __device__ __forceinline__ void splat8(float v, half8& hi, half8& lo) {
     const half_t h = (half_t)v;

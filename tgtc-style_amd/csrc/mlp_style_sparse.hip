@@ -21,6 +21,13 @@
 //                                                 read or written.  Everything else -- r = live[i] / N, z[k,r], o + t d, the
 //                                                 MFMA sequence, the clamped columns masked from every store -- is shared
 //                                                 source, so a live sample has the bits it has in the scattered form.
+//   styled_rays_sparse_kernel<C, COMPACT, true>   the FOLD form of either (tgtc_render_rays_styled_sparse_folded,
+//                                                 tgtc_restyle_rays_folded): K latents that are the same for every sample.
+//                                                 Their k-step in each of the 13 style layers is a per-latent bias table
+//                                                 (tgtc_style_fold_latents, mlp_style.hip); the kernel walks the handle's
+//                                                 streams packed without that k-step and swaps latent k's table into the
+//                                                 LDS bias region at the top of each latent iteration.  With z = 0 the
+//                                                 bits of the unfolded form with a zero latent.
 //
 // Per latent this is the MFMA sequence of styled_rays_multi_kernel on the same operands, and a column (sample) of an MFMA
 // does not depend on the other columns of its tile, so a live sample carries the bits of the dense kernels.
@@ -52,6 +59,7 @@ struct StyledSparseArgs {
     float* rgb;                // [K,R,N,3], zero-filled by the caller; compact form: [K,count,3], every entry written
     const float* ts_live;      // compact form: [count] depths of the list's samples
     unsigned count;            // compact form: the list's length
+    const char* folded;        // folded forms: [K] pair bias tables of kStylePairBiasBytes (tgtc_style_fold_latents); z is not read
 };
 
 // concat | style, both chunk aligned (as PairMap of mlp_style_multi.hip)
@@ -64,12 +72,32 @@ struct SparsePairMap {
     static constexpr int chunk0(int i) { return i == 0 ? 0 : i == 1 ? F_STYLE / C::FPC : (1 << 30); }
     static_assert(kConcatFrags % C::FPC == 0, "concat stream must end on a chunk boundary");
 };
+// the same over the streams packed without the latent k-steps
+template <class C>
+struct SparsePairFoldMap {
+    static constexpr int F_CONCAT = 0;
+    static constexpr int F_STYLE = kConcatFoldFrags;
+    static constexpr int NFRAG = F_STYLE + kStyleFoldFrags;
+    static constexpr int NSEG = 2;
+    static constexpr int chunk0(int i) { return i == 0 ? 0 : i == 1 ? F_STYLE / C::FPC : (1 << 30); }
+    static_assert(kConcatFoldFrags % C::FPC == 0, "concat stream must end on a chunk boundary");
+};
 
-template <class C, bool COMPACT>
+// FOLD: the latents are constant over the launch.  a.z is not read and no latent operand exists; a.concat_stream /
+// a.style_stream are the handle's streams without the latent k-steps, and latent k's bias table a.folded[k] takes the place
+// of the handle's pair bias table in LDS.  The LDS has room for one table (ring + NeRF bias + pair bias = 160 KiB), so with
+// K > 1 table k is brought into the same region at the top of every latent iteration:
+//   * behind the barrier that opens the iteration -- every wave has then finished the last bias read (style layer 7) of
+//     the latent before, and of the tile before;
+//   * in front of ws.prologue()'s chunk requests -- vmcnt retires loads in issue order, so every counted wait behind them
+//     (start_ring: chunks 0 and 1 landed) finds the table's two requests landed as well, with the counts unchanged, and
+//     the barrier of start_ring makes all waves' pieces visible before the first bias read of the concat MLP.
+// With K = 1 the table loaded at the kernel's start stays.
+template <class C, bool COMPACT, bool FOLD = false>
 __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_sparse_kernel(StyledSparseArgs a) {
     constexpr int NCT = C::NCT;
     constexpr bool SPLIT = C::SPLIT;
-    using Map = SparsePairMap<C>;
+    using Map = std::conditional_t<FOLD, SparsePairFoldMap<C>, SparsePairMap<C>>;
     using L = NerfLayout;
     __shared__ __attribute__((aligned(16))) char smem[kRingBytes + kNerfBiasBytes + kStylePairBiasBytes];
 
@@ -99,9 +127,10 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
     for (int j = 0; j < kNerfBiasBytes / (C::NWAVES * 1024); ++j)
         __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.nerf_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
                                          TGTC_LPTR(smem + kRingBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+    const char* const first_table = FOLD ? a.folded : a.pair_bias;
 #pragma unroll
     for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
-        __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.pair_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
+        __builtin_amdgcn_global_load_lds(TGTC_GPTR(first_table + (j * C::NWAVES + wave) * 1024 + lane * 16),
                                          TGTC_LPTR(smem + kRingBytes + kNerfBiasBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
     const lds_cptr nerf_bias = opaque((lds_cptr)smem + kRingBytes + 16 * g);
     const lds_cptr pair_bias = opaque((lds_cptr)smem + kRingBytes + kNerfBiasBytes + 16 * g);
@@ -183,6 +212,53 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
             });
         }
 
+        if constexpr (FOLD) {
+            for (int k = 0; k < a.K; ++k) {
+                // every wave must be done with the previous stream, and with the previous latent's bias table
+                __builtin_amdgcn_s_barrier();
+                if (a.K > 1) {
+                    const char* table = a.folded + (size_t)k * kStylePairBiasBytes;
+#pragma unroll
+                    for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
+                        __builtin_amdgcn_global_load_lds(TGTC_GPTR(table + (j * C::NWAVES + wave) * 1024 + lane * 16),
+                                                         TGTC_LPTR(smem + kRingBytes + kNerfBiasBytes + (j * C::NWAVES + wave) * 1024),
+                                                         16, 0, 0);
+                }
+                ws.prologue();
+                ws.start();
+                concat_mlp_folded<C, Map::F_CONCAT, 0>(ws, pair_bias, pe_h, pe_l, Xh, Xl, Yh, Yl);
+                // ---- style layer 0 on [remap (slab B -> X) | concat_features (Y) | pe]; outputs stream to slab A
+                stash_load<C>(slab + a.stash2_delta, Xh, Xl);
+                {
+                    half8 Bh[18][NCT], Bl[18][NCT];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) append<C>(Bh, Bl, i, Xh[i], Xl[i]);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) append<C>(Bh, Bl, 8 + i, Yh[i], Yl[i]);
+                    append<C>(Bh, Bl, 16, pe_h[0], pe_l[0]);
+                    append<C>(Bh, Bl, 17, pe_h[1], pe_l[1]);
+                    half8 Th[NCT], Tl[NCT];
+                    dense_layer<C, Map::F_STYLE + style_fold_frag0(0), 18, 16, kConcatBiasFloats + style_bias0(0)>(
+                        ws, pair_bias, Bh, Bl, [&](auto rt_, auto c_, auto h_, const float4v& acc) {
+                            constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value, hf = decltype(h_)::value;
+                            store_act<C, rt, hf>(acc, Th[c], Tl[c]);
+                            if constexpr ((rt & 1) && hf == 1) stash_store<C>(slab, rt / 2, c, Th[c], Tl[c]);
+                        });
+                }
+                stash_load<C>(slab, Xh, Xl);
+                float* rgb_k = a.rgb + (long long)k * a.M * 3;
+                style_tail_folded<C, Map::F_STYLE, kConcatBiasFloats>(ws, pair_bias, pe_h, pe_l, Xh, Xl, Yh, Yl,
+                                                                      [&](auto c_, auto h_, const float4v& acc) {
+                                                                          constexpr int c = decltype(c_)::value, hf = decltype(h_)::value;
+                                                                          if (g == 0 && (own >> c & 1)) {
+                                                                              const unsigned at = COMPACT ? i_wave + c * 16 + n : sidx[c];
+#pragma unroll
+                                                                              for (int r = 2 * hf; r < (hf ? 3 : 2); ++r)
+                                                                                  rgb_k[(size_t)at * 3 + r] = 1.0f / (1.0f + expf(-acc[r]));
+                                                                          }
+                                                                      });
+            }
+        } else
         for (int k = 0; k < a.K; ++k) {
             // ---- latent k of the tile's rays
             float zsum[NCT];
@@ -256,12 +332,26 @@ using CfgFast = MlpCfg<8, 2, false, 4>;  // the geometries of styled_rays_multi_
 using CfgExact = MlpCfg<8, 1, true, 4>;
 
 // Each of the four instances (fp16x3 / fp16, scattered / compact) is compiled in a translation unit of its own -- this
-// source as it is, with -DTGTC_TU_FP16_ONLY, -DTGTC_TU_COMPACT or both -- so that the kernels build in parallel.
-template <class C, bool COMPACT>
+// source as it is, with -DTGTC_TU_FP16_ONLY, -DTGTC_TU_COMPACT or both -- so that the kernels build in parallel.  The four
+// folded instances likewise, with -DTGTC_TU_FOLD in front of the same three combinations and of none.
+template <class C, bool COMPACT, bool FOLD = false>
 void launch_styled_rays_sparse(unsigned grid, const StyledSparseArgs& a, hipStream_t st) {
-    styled_rays_sparse_kernel<C, COMPACT><<<grid, C::NWAVES * 64, 0, st>>>(a);
+    styled_rays_sparse_kernel<C, COMPACT, FOLD><<<grid, C::NWAVES * 64, 0, st>>>(a);
 }
-#if defined(TGTC_TU_FP16_ONLY) && defined(TGTC_TU_COMPACT)
+#if defined(TGTC_TU_FOLD)
+#ifdef TGTC_TU_FP16_ONLY
+using CfgFold = CfgFast;
+#else
+using CfgFold = CfgExact;
+#endif
+#ifdef TGTC_TU_COMPACT
+constexpr bool kFoldCompact = true;
+#else
+constexpr bool kFoldCompact = false;
+#endif
+template void launch_styled_rays_sparse<CfgFold, kFoldCompact, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+}  // namespace tgtc
+#elif defined(TGTC_TU_FP16_ONLY) && defined(TGTC_TU_COMPACT)
 template void launch_styled_rays_sparse<CfgFast, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 }  // namespace tgtc
 #elif defined(TGTC_TU_COMPACT)
@@ -274,6 +364,10 @@ template void launch_styled_rays_sparse<CfgFast, false>(unsigned, const StyledSp
 extern template void launch_styled_rays_sparse<CfgFast, false>(unsigned, const StyledSparseArgs&, hipStream_t);
 extern template void launch_styled_rays_sparse<CfgExact, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 extern template void launch_styled_rays_sparse<CfgFast, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, false, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, false, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, true, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, true, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------ compaction
 // The plane of M weights is cut into kCompactParts contiguous ranges of `span` samples (a multiple of the block size).
@@ -466,5 +560,51 @@ int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const 
     return TGTC_OK;
 }
 
+// The two impls above over latents that are constant over the launch: `folded` holds the K bias tables of
+// tgtc_style_fold_latents, the streams are the handle's folded pair, and no latent is read (tgtc_styled_forward_list_folded,
+// tgtc_render_rays_styled_sparse_folded; tgtc_restyle_rays_folded).  The callers have checked the sizes and precisions.
+static StyledSparseArgs folded_args(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const void* folded, int K, int64_t R, int N, const uint32_t* live, float* rgb) {
+    StyledSparseArgs a{};
+    a.nerf_bias = nerf->dev, a.nerf_stream = nerf->dev + nerf->bias_bytes;
+    a.pair_bias = style->dev, a.folded = static_cast<const char*>(folded);
+    a.concat_stream = style->dev + style->fold_stream_off, a.style_stream = style->dev + style->fold_stream2_off;
+    a.stash = style->dev + style->stash_off, a.stash2_delta = (long long)(style->stash2_off - style->stash_off);
+    a.R = R, a.N = N, a.K = K, a.rays_o = rays_o, a.rays_d = rays_d, a.live = live, a.rgb = rgb;
+    return a;
+}
+
+int styled_forward_list_folded_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const float* ts, const void* folded, int K, int64_t R, int N, const uint32_t* live,
+                                    const uint32_t* n_live, float* rgb, hipStream_t st) {
+    StyledSparseArgs a = folded_args(nerf, style, rays_o, rays_d, folded, K, R, N, live, rgb);
+    a.M = R * (int64_t)N, a.ts = ts, a.n_live = n_live;
+    if (nerf->precision == TGTC_PREC_FP16) {
+        const long long tiles = (a.M + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgFast, false, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    } else {
+        const long long tiles = (a.M + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgExact, false, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    }
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+int styled_restyle_live_folded_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
+                                    int64_t count, float* rgb_live, hipStream_t st) {
+    StyledSparseArgs a = folded_args(nerf, style, rays_o, rays_d, folded, K, R, N, live, rgb_live);
+    a.M = count, a.ts_live = ts_live, a.count = (unsigned)count;
+    if (nerf->precision == TGTC_PREC_FP16) {
+        const long long tiles = (count + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgFast, true, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    } else {
+        const long long tiles = (count + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgExact, true, true>((unsigned)(tiles < style->n_wg ? tiles : style->n_wg), a, st);
+    }
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
 }  // namespace tgtc
-#endif  // TGTC_TU_FP16_ONLY || TGTC_TU_COMPACT
+#endif  // TGTC_TU_FOLD || TGTC_TU_FP16_ONLY || TGTC_TU_COMPACT

@@ -36,6 +36,13 @@ int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const doub
 int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
                              const float* z, int K, int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count,
                              float* rgb_live, hipStream_t st);
+int style_fold_latents_impl(const tgtc_net* style, const float* z, int K, float* folded, hipStream_t st);
+int styled_forward_list_folded_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const float* ts, const void* folded, int K, int64_t R, int N, const uint32_t* live,
+                                    const uint32_t* n_live, float* rgb, hipStream_t st);
+int styled_restyle_live_folded_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                    const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
+                                    int64_t count, float* rgb_live, hipStream_t st);
 int launch_composite_live(const uint32_t* ray_start, const uint32_t* live, const float* w_live, const float* rgb_live, int64_t R,
                           int N, int K, int64_t count, float* rgb_exp, hipStream_t st);
 int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w_f, const float* t_fine, int64_t R, int N,
@@ -554,6 +561,133 @@ extern "C" int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, co
     // 1. trunk + concat MLP + style MLP over the cached list into the compact colour planes (nothing to launch for an empty list)
     if (count > 0) {
         rc = styled_restyle_live_impl(fine, style, rays_o, rays_d, z, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        if (rc) return rc;
+    }
+    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
+    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
+    if (rc) return rc;
+    // 3. the depth image
+    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return TGTC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frame-constant latents
+// The culled render and the restyle for latents that do not depend on the ray: z [K,32].  The latent k-step of every layer
+// of the two style networks is folded into K bias tables (tgtc_style_fold_latents, mlp_style.hip) kept in one more plane
+// at the end of the workspace, and the folded instances of the indexed kernels (mlp_style_sparse.hip) run on the streams
+// packed without that k-step.  Everything else is the unfolded sibling's.
+
+extern "C" int tgtc_styled_forward_list_folded(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o,
+                                               const double* rays_d, const float* ts, const void* folded, int K, int64_t R,
+                                               int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
+    TGTC_REQUIRE(K >= 1, "styled_forward_list_folded: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(R >= 0 && N >= 1, "styled_forward_list_folded: bad argument");
+    constexpr int64_t kLimit = (int64_t)1 << 31;
+    if (R >= kLimit || R * (int64_t)N >= kLimit || R * (int64_t)N * K >= kLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "styled_forward_list_folded: K x R x N >= 2^31 in one launch (chunk the rays)");
+    TGTC_REQUIRE(nerf && style, "styled_forward_list_folded: null handle");
+    TGTC_REQUIRE(nerf->kind == 0 && style->kind == 1, "styled_forward_list_folded: nerf must be a NeRF handle, style a style handle");
+    TGTC_REQUIRE(nerf->precision == style->precision,
+                 "styled_forward_list_folded: NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && folded && live && n_live && rgb, "styled_forward_list_folded: null pointer");
+    return styled_forward_list_folded_impl(nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live, rgb, as_stream(stream));
+}
+
+extern "C" size_t tgtc_render_styled_sparse_folded_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K) {
+    if (R < 0 || n_coarse < 0 || n_fine < 0 || K < 1) return 0;
+    return SparseWorkspace(nullptr, R, n_coarse, n_fine, K).total + align256(tgtc_style_folded_bytes(K));
+}
+
+extern "C" int tgtc_render_rays_styled_sparse_folded(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                                     const double* rays_o, const double* rays_d, const float* z, int K,
+                                                     int64_t R, int n_coarse, int n_fine, float near_, float far_,
+                                                     const float* jitter, float min_weight, void* workspace,
+                                                     size_t workspace_bytes, float* rgb_fine, float* t_fine,
+                                                     uint32_t* live_count, void* stream) {
+    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse_folded: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse_folded: min_weight must be >= 0 and not NaN (got %g)",
+                 (double)min_weight);
+    TGTC_REQUIRE(R >= 0, "render_rays_styled_sparse_folded: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse_folded: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(coarse && fine && style, "render_rays_styled_sparse_folded: null handle");
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "render_rays_styled_sparse_folded: coarse and fine must be NeRF handles, style a style handle");
+    TGTC_REQUIRE(fine->precision == style->precision,
+                 "render_rays_styled_sparse_folded: fine NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse_folded: null pointer");
+    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
+    const size_t need = sw.total + align256(tgtc_style_folded_bytes(K));
+    TGTC_REQUIRE(workspace_bytes >= need, "render_rays_styled_sparse_folded: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + sw.total);
+    const MultiWorkspace& ws = sw.m;
+    hipStream_t st = as_stream(stream);
+    // 0. the K bias tables
+    int rc = style_fold_latents_impl(style, z, K, folded, st);
+    if (rc) return rc;
+    // 1-4. everything that depends on the ray alone
+    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
+                      stream);
+    if (rc) return rc;
+    // 5. dead samples keep colour +0
+    TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
+    // 6. trunk + folded concat MLP + folded style MLP over the list
+    rc = styled_forward_list_folded_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    if (rc) return rc;
+    // 7. compositing over the shared sigma / depths
+    for (int k = 0; k < K; ++k) {
+        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, nullptr,
+                              nullptr, st);
+        if (rc) return rc;
+    }
+    return TGTC_OK;
+}
+
+extern "C" size_t tgtc_restyle_folded_workspace_bytes(int64_t count, int K) {
+    if (count < 0 || K < 1) return 0;
+    return tgtc_restyle_workspace_bytes(count, K) + align256(tgtc_style_folded_bytes(K));
+}
+
+extern "C" int tgtc_restyle_rays_folded(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                        const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                                        size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes,
+                                        float* rgb_fine, float* t_fine, void* stream) {
+    TGTC_REQUIRE(K >= 1, "restyle_rays_folded: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(R >= 0 && count >= 0, "restyle_rays_folded: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt || R == 0, "restyle_rays_folded: count %lld exceeds the %lld samples", (long long)count,
+                 (long long)(R * nt));
+    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded: K x count >= 2^31 (fewer latents per call)");
+    TGTC_REQUIRE(fine && style, "restyle_rays_folded: null handle");
+    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays_folded: fine must be a NeRF handle, style a style handle");
+    TGTC_REQUIRE(fine->precision == style->precision,
+                 "restyle_rays_folded: fine NeRF and style nets were packed with different precisions");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays_folded: null pointer");
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays_folded: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    const size_t need = tgtc_restyle_folded_workspace_bytes(count, K);
+    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays_folded: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    float* rgb_live = static_cast<float*>(workspace);
+    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
+    int rc;
+    // 1. the K bias tables, then trunk + folded concat MLP + folded style MLP over the cached list (nothing to launch for an
+    //    empty list)
+    if (count > 0) {
+        rc = style_fold_latents_impl(style, z, K, folded, st);
+        if (rc) return rc;
+        rc = styled_restyle_live_folded_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
         if (rc) return rc;
     }
     // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0

@@ -73,7 +73,9 @@ _SIGNATURES = {
 _RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_float, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
              "tgtc_render_styled_multi_workspace_bytes": c_size_t,
              "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
-             "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t}
+             "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t,
+             "tgtc_style_folded_bytes": c_size_t, "tgtc_render_styled_sparse_folded_workspace_bytes": c_size_t,
+             "tgtc_restyle_folded_workspace_bytes": c_size_t}
 _OPTIONAL = {
     "tgtc_style_create": [ctypes.POINTER(Linear), c_int, ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],
     "tgtc_concat_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
@@ -99,6 +101,17 @@ _OPTIONAL = {
     "tgtc_restyle_workspace_bytes": [c_int64, c_int],
     "tgtc_restyle_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
                           c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_style_folded_bytes": [c_int],
+    "tgtc_style_fold_latents": [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
+    "tgtc_styled_forward_list_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_render_styled_sparse_folded_workspace_bytes": [c_int64, c_int, c_int, c_int],
+    "tgtc_render_rays_styled_sparse_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                              c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p,
+                                              c_void_p, c_void_p, c_void_p],
+    "tgtc_restyle_folded_workspace_bytes": [c_int64, c_int],
+    "tgtc_restyle_rays_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
+                                 c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -202,25 +202,39 @@ class RayRenderer:
         first, then the NeRF trunk and the style networks only on the samples whose compositing weight exceeds min_weight
         (csrc/mlp_style_sparse.hip).  0 reproduces the images bit for bit; a positive value changes each ray by at most the
         sum of its dropped weights and leaves t alone.  The result then carries "live": the number of samples the style
-        networks ran on, a device scalar (int32 view of the library's uint32) that is NOT synchronised."""
+        networks ran on, a device scalar (int32 view of the library's uint32) that is NOT synchronised.
+
+        zs float [K,32] (with a min_weight): K latents that are the same for every ray.  Takes
+        tgtc_render_rays_styled_sparse_folded: the latent columns of the style networks become K bias tables and the kernels
+        run without the latent k-steps; no [K,R,32] plane exists.  Results differ from the [K,R,32] call with the rows
+        repeated within the precision's error (zs = 0: bit for bit).  The dense multi-latent kernel has no such form: a
+        2-D zs with min_weight=None is a ValueError."""
+        if zs is not None and zs.dim() == 2 and min_weight is None:
+            raise ValueError("zs [K,32] (latents constant over the rays) needs a min_weight: the dense multi-latent kernel has "
+                             "no folded form")
         hip.require_gpu(rays_o, rays_d, zs)
         lib = hip.load()
         if self.style is None or zs is None:
-            raise ValueError("render_latents needs a style pair and zs [K,R,32]")
+            raise ValueError("render_latents needs a style pair and zs [K,R,32] or [K,32]")
         if n_fine <= 0:
             raise ValueError("N_samples_fine must be > 0 (the reference render paths dereference None otherwise)")
         rays_o = rays_o.to(torch.float64).contiguous()
         rays_d = rays_d.to(torch.float64).contiguous()
         R, dev = rays_o.shape[0], rays_o.device
         zs = zs.to(torch.float32).contiguous()
-        if zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
+        folded = zs.dim() == 2
+        if folded:
+            if zs.shape[0] < 1 or zs.shape[1] != 32:
+                raise ValueError("zs must be [K,32] with K >= 1, got %s" % list(zs.shape))
+        elif zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
             raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
         K = zs.shape[0]
         if min_weight is not None:
             min_weight = float(min_weight)
             if not min_weight >= 0:
                 raise ValueError("min_weight must be >= 0 (got %r)" % min_weight)
-            need = lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, K)
+            need = (lib.tgtc_render_styled_sparse_folded_workspace_bytes if folded else
+                    lib.tgtc_render_styled_sparse_workspace_bytes)(R, n_coarse, n_fine, K)
         else:
             need = lib.tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K)
         if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
@@ -233,11 +247,10 @@ class RayRenderer:
             jitter = jitter.to(torch.float32).contiguous()
         if min_weight is not None:
             live = torch.zeros((), device=dev, dtype=torch.int32)
-            hip.check(lib.tgtc_render_rays_styled_sparse(self.coarse.packed().handle, self.fine.packed().handle,
-                                                         self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs),
-                                                         K, R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
-                                                         min_weight, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t),
-                                                         hip.ptr(live), hip.stream()))
+            call = lib.tgtc_render_rays_styled_sparse_folded if folded else lib.tgtc_render_rays_styled_sparse
+            hip.check(call(self.coarse.packed().handle, self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o),
+                           hip.ptr(rays_d), hip.ptr(zs), K, R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
+                           min_weight, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(live), hip.stream()))
             return {"rgb": rgb, "t": t, "live": live}
         hip.check(lib.tgtc_render_rays_styled_multi(self.coarse.packed().handle, self.fine.packed().handle,
                                                     self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K,
@@ -281,7 +294,9 @@ class RayRenderer:
         host int).  One launch of the compact indexed style kernel over the cached list and one compositing launch; the
         bits of `render_latents(..., min_weight=cache.min_weight)`.  rays_o / rays_d must be the rays the cache was built
         from (it stores depths, not positions).  ValueError before any launch if R, a given n_coarse + n_fine or a given
-        `key` does not match the cache."""
+        `key` does not match the cache.
+        zs float [K,32]: K latents that are the same for every ray, through tgtc_restyle_rays_folded (see render_latents);
+        the same cache serves both forms."""
         hip.require_gpu(rays_o, rays_d, zs, cache.buffer)
         lib = hip.load()
         if self.style is None:
@@ -298,20 +313,24 @@ class RayRenderer:
         rays_d = rays_d.to(torch.float64).contiguous()
         dev = rays_o.device
         zs = zs.to(torch.float32).contiguous()
-        if zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
+        folded = zs.dim() == 2
+        if folded:
+            if zs.shape[0] < 1 or zs.shape[1] != 32:
+                raise ValueError("zs must be [K,32] with K >= 1, got %s" % list(zs.shape))
+        elif zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
             raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
         K = zs.shape[0]
-        need = lib.tgtc_restyle_workspace_bytes(cache.count, K)
+        need = (lib.tgtc_restyle_folded_workspace_bytes if folded else lib.tgtc_restyle_workspace_bytes)(cache.count, K)
         if self._ws_restyle is None or self._ws_restyle.numel() < need or self._ws_restyle.device != dev:
             self._ws_restyle = None
             self._ws_restyle = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         ws = self._ws_restyle
         rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
-        hip.check(lib.tgtc_restyle_rays(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
-                                        hip.ptr(zs), K, R, cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer),
-                                        cache.buffer.numel(), cache.count, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t),
-                                        hip.stream()))
+        call = lib.tgtc_restyle_rays_folded if folded else lib.tgtc_restyle_rays
+        hip.check(call(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R,
+                       cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(ws),
+                       ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
         return {"rgb": rgb, "t": t, "live": cache.count}
 
 
@@ -519,7 +538,7 @@ def _cached_geometry(renderer, directory, name, key, build):
 
 
 def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None, geometry_cache=None,
-                         geometry_tag=None):
+                         geometry_tag=None, fold_latents=False):
     """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
     `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
     style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
@@ -528,10 +547,14 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     min_weight: RayRenderer.render_latents' (None: the style networks run on every sample).
     geometry_cache: a directory of GeometryCache files, one per (frame, pixel range of a call).  A file with a matching key is
     loaded and the call becomes `RayRenderer.restyle`; otherwise the geometry is built, saved there and restyled.  The
-    images are those of min_weight (None counts as 0) without the cache, bit for bit."""
+    images are those of min_weight (None counts as 0) without the cache, bit for bit.
+    fold_latents: the latent model is evaluated on ONE row per style and the calls take zs [K,32] (RayRenderer.render_latents /
+    restyle: the folded kernels); needs a min_weight or a geometry_cache, and every ray of a call in the same frame."""
     ds = dataloader.dataset
     if renderer is None or not hasattr(ds, 'frame_batches'):
         raise ValueError("share_geometry needs renderer=RayRenderer(...) and a dataset with the frame_batches hook")
+    if fold_latents and min_weight is None and geometry_cache is None:
+        raise ValueError("fold_latents needs a min_weight or a geometry_cache (the dense multi-latent kernel has no folded form)")
     frame_num, h, w, styles = ds.cps_valid.shape[0], ds.h, ds.w, ds.style_num
     res = _local_res(ds, h * w)
     nt = args.N_samples + args.N_samples_fine
@@ -549,8 +572,15 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
         for lo in range(0, R, per_call):
             sl = slice(lo, min(lo + per_call, R))
             frame_ids = b['frame_id'][sl].long()
-            zs = torch.stack([latents_model_1(style_ids=torch.full_like(frame_ids, sid), frame_ids=frame_ids,
-                                              type=args.dataset_type) for sid in range(styles)])
+            if fold_latents:
+                if not bool((frame_ids == frame_ids[0]).all()):
+                    raise ValueError("fold_latents: the rays of a call belong to more than one frame")
+                one = frame_ids[:1]
+                zs = torch.cat([latents_model_1(style_ids=torch.full_like(one, sid), frame_ids=one, type=args.dataset_type)
+                                for sid in range(styles)])       # [K,32]
+            else:
+                zs = torch.stack([latents_model_1(style_ids=torch.full_like(frame_ids, sid), frame_ids=frame_ids,
+                                                  type=args.dataset_type) for sid in range(styles)])
             jitter = b['jitter'][sl] if 'jitter' in b else torch.rand(frame_ids.shape[0], args.N_samples, device=device)
             if geometry_cache is not None:
                 if 'jitter' not in b:
@@ -582,7 +612,7 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
 
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
                  device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
-                 share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None):
+                 share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None, fold_latents=False):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
     Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
@@ -591,10 +621,12 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     weight exceeds it, see RayRenderer.render_latents; None runs them on every sample.
     geometry_cache (share_geometry only): a directory in which the ray-only half of every call is kept and reused, see
     _render_style_shared; geometry_tag: a string that goes into the cache keys (what the driver cannot see, e.g. the NeRF
-    checkpoint step)."""
+    checkpoint step); fold_latents (share_geometry only): one latent per (style, frame), see _render_style_shared."""
     _require_fine(args)
     if geometry_cache is not None and not share_geometry:
         raise ValueError("geometry_cache needs share_geometry=True (the cache belongs to the walk by frames)")
+    if fold_latents and not share_geometry:
+        raise ValueError("fold_latents needs share_geometry=True (one latent per style and frame belongs to the walk by frames)")
     latents_model_1.sigma_scale = sigma_scale
     if sv_path is not None:
         os.makedirs(sv_path, exist_ok=True)
@@ -602,7 +634,7 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     ds.mode = 'valid_style'
     if share_geometry:
         return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight,
-                                    geometry_cache=geometry_cache, geometry_tag=geometry_tag)
+                                    geometry_cache=geometry_cache, geometry_tag=geometry_tag, fold_latents=fold_latents)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0

@@ -273,7 +273,7 @@ def train(args):
             dataset.mode = 'valid_style'
             rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, share_geometry=args.share_geometry,
                                    geometry_cache=args.geometry_cache or None, geometry_tag="nerf_step=%d" % nerf_step,
-                                   **common, **styled)
+                                   fold_latents=args.fold_latents, **common, **styled)
             print('Done, saving to', out)
             return out
         if args.render_train_style:
@@ -306,6 +306,12 @@ def main(argv=None):
     if args.geometry_cache and not args.share_geometry:
         raise SystemExit("train_tgtcs: --geometry_cache needs --share_geometry (the cache is kept per frame, for all styles "
                          "of the frame; add --share_geometry or drop --geometry_cache)")
+    if args.fold_latents and not (args.render_valid_style and args.share_geometry):
+        raise SystemExit("train_tgtcs: --fold_latents needs --render_valid_style --share_geometry (one latent per style and "
+                         "frame belongs to the walk by frames)")
+    if args.fold_latents and not (args.cull_weight >= 0 or args.geometry_cache):
+        raise SystemExit("train_tgtcs: --fold_latents needs --cull_weight >= 0 or --geometry_cache (the folded kernels are "
+                         "those of the culled render and of the restyle; the dense multi-latent kernel has no folded form)")
     if args.expname is None:
         raise SystemExit("train_tgtcs: --expname (or --config) is required")
     try:
