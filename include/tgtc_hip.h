@@ -403,6 +403,56 @@ int tgtc_restyle_rays_folded(const tgtc_net* fine, const tgtc_net* style, const 
                              const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
                              int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream);
 
+/* ------------------------------------------------------------------ restyle from cached trunk features, without the NeRF network
+ * One ray-only piece is still recomputed by every tgtc_restyle_rays: the fine NeRF trunk (layers 0-7, the sigma layer's
+ * fragments, base_remap_layer), 556 800 multiply-accumulates per live sample against 950 112 per latent -- 1 096 fragments
+ * against 656 + 1 209 (576 + 1 096 folded).  tgtc_geometry_trunk runs it once over the cached list and keeps base_remap in a
+ * caller-owned TRUNK PLANE beside the cache; tgtc_restyle_rays_trunk[_folded] restyle from cache + plane with the style
+ * handle alone: the concat MLP, style layer 0 on [plane | concat features | encoding | mean z] and the style tail.  NO NeRF
+ * HANDLE, coarse or fine, is involved in a restyle from the plane.
+ * The price is memory: one 128 KiB tile per workgroup tile of the list, i.e. 1 KiB per live sample in TGTC_PREC_FP16X3 and
+ *   512 B in TGTC_PREC_FP16 (a 400 x 400 frame with 3.04 M live samples: 3.1 GB / 1.6 GB, against 38 MB for the cache).  It is
+ *   a mode the caller asks for; nothing selects it.
+ * Plane layout: the library's operand-fragment layout, the bytes the style kernels park in the handle's slab.  With S = 128
+ *   (FP16X3) or 256 (FP16) samples per tile, NCT = S / 128 column tiles per wave and P = 2 (FP16X3: hi, then lo) or 1 parts,
+ *   thread tid (0..511) of tile t owns the 16 bytes (its 8 halves of the MFMA B fragment of k-step ks, whose column tid % 16 is
+ *   list entry t S + (tid / 64) 16 NCT + 16 c + tid % 16) at
+ *       t x 131072 + ((ks x NCT + c) x P + p) x 8192 + tid x 16,      ks = 0..7, c = 0..NCT-1, p = 0..P-1.
+ *   Every byte of every tile is written: columns past the list's end hold the last live sample's fragments.  No zero-fill is
+ *   needed and two builds are byte-equal.  The plane is position independent (it may be copied, saved and reloaded) and valid
+ *   ONLY for the precision and the cached list it was built for.  A plane built in the other precision that happens to be large
+ *   enough CANNOT be detected here: the caller keeps the precision beside the plane (the Python layer does and checks it).
+ *
+ * tgtc_geometry_trunk_bytes(precision, count): ceil(count / S) x 131072; 0 for count <= 0 or any other precision.
+ * tgtc_geometry_trunk: reads live and ts_live of a packed cache (tgtc_geometry_pack) and writes the plane with ONE launch of the
+ *   trunk form of the compact indexed kernel (csrc/mlp_style_sparse.hip) on `fine`, which must be the fine handle of the build.
+ *   No coarse pass, no sigma pass, no synchronisation, no style handle; the slab of no handle is touched.  count == 0: nothing
+ *   is launched and trunk may be NULL.
+ * tgtc_restyle_rays_trunk / tgtc_restyle_rays_trunk_folded: the arguments, workspaces (tgtc_restyle_workspace_bytes /
+ *   tgtc_restyle_folded_workspace_bytes) and results of tgtc_restyle_rays / tgtc_restyle_rays_folded without the fine handle and
+ *   with the plane; z float [K,R,32] / [K,32].  They finish with the same compositing launch and the same depth copy.  The
+ *   plane is only read.  count == 0: no kernel but the compositing is launched, trunk may be NULL, rgb_fine is +0, t_fine is copied.
+ * Identity: rgb_fine, t_fine are the BITS of tgtc_restyle_rays / tgtc_restyle_rays_folded on the same cache when the plane was
+ *   built by tgtc_geometry_trunk with the fine handle those calls would be given, packed in the style handle's precision: a
+ *   live sample is the same column of the same MFMA sequence on the same operands, and base_remap's half8 values make a
+ *   round trip through memory either way (the slab there, the plane here).
+ * Errors (every check returns before a device is touched): null pointers, K < 1, R < 0, count < 0, count > R x N, n_coarse < 3,
+ *   n_fine < 1, a wrong handle kind, a cache, plane or workspace below its size function (the plane's by the handle's
+ *   precision) -> TGTC_ERR_ARG;  R x N >= 2^31, K x count >= 2^31, a fine handle in TGTC_PREC_FP16_FP6 given to
+ *   tgtc_geometry_trunk -> TGTC_ERR_UNSUPPORTED;  R == 0 -> TGTC_OK.  The size and range checks come before the handle is looked at.
+ * Scratch slab: the restyles use slab region A of the STYLE HANDLE; launches on one style handle must not overlap. */
+size_t tgtc_geometry_trunk_bytes(int precision, int64_t count);
+int tgtc_geometry_trunk(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse, int n_fine,
+                        const void* cache, size_t cache_bytes, int64_t count, void* trunk, size_t trunk_bytes, void* stream);
+int tgtc_restyle_rays_trunk(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                            int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
+                            const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
+                            float* rgb_fine, float* t_fine, void* stream);
+int tgtc_restyle_rays_trunk_folded(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z, int K,
+                                   int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
+                                   const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
+                                   float* rgb_fine, float* t_fine, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

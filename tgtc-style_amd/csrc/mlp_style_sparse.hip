@@ -28,6 +28,15 @@
 //                                                 streams packed without that k-step and swaps latent k's table into the
 //                                                 LDS bias region at the top of each latent iteration.  With z = 0 the
 //                                                 bits of the unfolded form with a zero latent.
+//   styled_rays_sparse_kernel<C, true, false, kPlaneBuild>   the trunk PRODUCER (tgtc_geometry_trunk): the compact form's
+//                                                 gather, encoding and NeRF trunk, with base_remap's operand fragments
+//                                                 stored to the caller's trunk plane (one kStashBytesPerWG tile per tile of
+//                                                 the list) instead of slab region B.  No style stream, no latent, no rgb.
+//   styled_rays_sparse_kernel<C, true, FOLD, kPlaneRead>     the plane CONSUMER (tgtc_restyle_rays_trunk[_folded]): the compact
+//                                                 form without its trunk -- no NeRF stream, no NeRF bias table -- reading
+//                                                 the tile's fragments from the plane where the others read slab region B.
+//                                                 The values make the same half8 round trip through memory, so the bits
+//                                                 of the compact form on the same list.
 //
 // Per latent this is the MFMA sequence of styled_rays_multi_kernel on the same operands, and a column (sample) of an MFMA
 // does not depend on the other columns of its tile, so a live sample carries the bits of the dense kernels.
@@ -60,7 +69,13 @@ struct StyledSparseArgs {
     const float* ts_live;      // compact form: [count] depths of the list's samples
     unsigned count;            // compact form: the list's length
     const char* folded;        // folded forms: [K] pair bias tables of kStylePairBiasBytes (tgtc_style_fold_latents); z is not read
+    char* plane;               // plane forms: ceil(count / SAMPLES_PER_WG) tiles of kStashBytesPerWG, base_remap in the slab's layout
 };
+
+// PLANE: where base_remap of a tile lives between the trunk and the latents.
+constexpr int kPlaneNone = 0;   // slab region B of the style handle, written and read by the same launch
+constexpr int kPlaneBuild = 1;  // the trunk alone, written to a.plane
+constexpr int kPlaneRead = 2;   // no trunk, read from a.plane
 
 // concat | style, both chunk aligned (as PairMap of mlp_style_multi.hip)
 template <class C>
@@ -93,13 +108,28 @@ struct SparsePairFoldMap {
 //     (start_ring: chunks 0 and 1 landed) finds the table's two requests landed as well, with the counts unchanged, and
 //     the barrier of start_ring makes all waves' pieces visible before the first bias read of the concat MLP.
 // With K = 1 the table loaded at the kernel's start stays.
-template <class C, bool COMPACT, bool FOLD = false>
+//
+// PLANE (compact form only): kPlaneBuild stops behind base_remap, which goes to tile `tile` of a.plane; kPlaneRead starts
+// behind it and loads the tile from a.plane.  A plane tile is slab region B's bytes at another base: thread tid owns the 16
+// bytes at tile * kStashBytesPerWG + ((ks * NCT + c) * P + p) * 8192 + tid * 16 (P = 2 parts, hi then lo, in split mode).  The
+// tile's byte offset is 64-bit: a frame's plane passes 2^32 bytes.  Every column is stored, the clamped ones (copies of the
+// last live sample) included, so a build writes every byte of every tile.
+//   * kPlaneRead has no trunk stream to take the ring's lane addresses from: ws is initialised on its own (the same values).
+//   * Its pair bias table is requested before the first ws.prologue(), so that stream's first counted wait and ring barrier
+//     cover it as the trunk's did.
+//   * Both forms end on a stream that has been walked to its last chunk: no LDS-DMA is in flight when a workgroup ends.
+template <class C, bool COMPACT, bool FOLD = false, int PLANE = kPlaneNone>
 __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_sparse_kernel(StyledSparseArgs a) {
+    static_assert(PLANE == kPlaneNone || COMPACT, "the plane belongs to a cached list");
+    static_assert(PLANE != kPlaneBuild || !FOLD, "the trunk sees no latent");
+    constexpr bool TRUNK = PLANE != kPlaneRead;    // the tile runs the NeRF trunk
+    constexpr bool STYLE = PLANE != kPlaneBuild;   // ... and the style networks
     constexpr int NCT = C::NCT;
     constexpr bool SPLIT = C::SPLIT;
     using Map = std::conditional_t<FOLD, SparsePairFoldMap<C>, SparsePairMap<C>>;
     using L = NerfLayout;
-    __shared__ __attribute__((aligned(16))) char smem[kRingBytes + kNerfBiasBytes + kStylePairBiasBytes];
+    constexpr int kPairBiasAt = kRingBytes + (TRUNK ? kNerfBiasBytes : 0);
+    __shared__ __attribute__((aligned(16))) char smem[kPairBiasAt + (STYLE ? kStylePairBiasBytes : 0)];
 
     // the list's length decides the tiles; a workgroup without one leaves before any LDS-DMA is issued (none may be in
     // flight when it ends), which is also what keeps live[n_live - 1] from being read when nothing is live
@@ -113,27 +143,44 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, n = lane & 15;
-    char* slab = a.stash + (size_t)blockIdx.x * kStashBytesPerWG + (size_t)tid * 16;    // this lane's 16-byte column, region A
+    // this lane's 16-byte column of slab region A (the trunk producer has no style handle and no slab)
+    char* slab = STYLE ? a.stash + (size_t)blockIdx.x * kStashBytesPerWG + (size_t)tid * 16 : nullptr;
+    // ... and of the tile's base_remap: slab region B, or the tile's own tile of the plane
+    auto remap_at = [&](unsigned tile) -> char* {
+        if constexpr (PLANE == kPlaneNone) return slab + a.stash2_delta;
+        else return a.plane + (size_t)tile * kStashBytesPerWG + (size_t)tid * 16;
+    };
 
     WeightStream<C, SingleStreamMap<kTrunkFrags>> wt;
     WeightStream<C, Map> ws;
-    const char* const trunk_streams[1] = {a.nerf_stream};
-    wt.init(trunk_streams, smem, wave, lane);
-    ws.src[0] = ws.lane_src(a.concat_stream, wave, lane);
-    ws.src[1] = ws.lane_src(a.style_stream, wave, lane);
-    ws.voff = wt.voff, ws.lds_wave = wt.lds_wave, ws.lane_lo = wt.lane_lo, ws.lane_hi = wt.lane_hi;
+    if constexpr (TRUNK) {
+        const char* const trunk_streams[1] = {a.nerf_stream};
+        wt.init(trunk_streams, smem, wave, lane);
+    }
+    if constexpr (STYLE && TRUNK) {
+        ws.src[0] = ws.lane_src(a.concat_stream, wave, lane);
+        ws.src[1] = ws.lane_src(a.style_stream, wave, lane);
+        ws.voff = wt.voff, ws.lds_wave = wt.lds_wave, ws.lane_lo = wt.lane_lo, ws.lane_hi = wt.lane_hi;
+    } else if constexpr (STYLE) {
+        const char* const pair_streams[2] = {a.concat_stream, a.style_stream};
+        ws.init(pair_streams, smem, wave, lane);
+    }
     // bias tables: loaded once per workgroup (LDS-DMA), visible after the first ring barrier
+    if constexpr (TRUNK) {
 #pragma unroll
-    for (int j = 0; j < kNerfBiasBytes / (C::NWAVES * 1024); ++j)
-        __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.nerf_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
-                                         TGTC_LPTR(smem + kRingBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
-    const char* const first_table = FOLD ? a.folded : a.pair_bias;
+        for (int j = 0; j < kNerfBiasBytes / (C::NWAVES * 1024); ++j)
+            __builtin_amdgcn_global_load_lds(TGTC_GPTR(a.nerf_bias + (j * C::NWAVES + wave) * 1024 + lane * 16),
+                                             TGTC_LPTR(smem + kRingBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+    }
+    if constexpr (STYLE) {
+        const char* const first_table = FOLD ? a.folded : a.pair_bias;
 #pragma unroll
-    for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
-        __builtin_amdgcn_global_load_lds(TGTC_GPTR(first_table + (j * C::NWAVES + wave) * 1024 + lane * 16),
-                                         TGTC_LPTR(smem + kRingBytes + kNerfBiasBytes + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+        for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
+            __builtin_amdgcn_global_load_lds(TGTC_GPTR(first_table + (j * C::NWAVES + wave) * 1024 + lane * 16),
+                                             TGTC_LPTR(smem + kPairBiasAt + (j * C::NWAVES + wave) * 1024), 16, 0, 0);
+    }
     const lds_cptr nerf_bias = opaque((lds_cptr)smem + kRingBytes + 16 * g);
-    const lds_cptr pair_bias = opaque((lds_cptr)smem + kRingBytes + kNerfBiasBytes + 16 * g);
+    const lds_cptr pair_bias = opaque((lds_cptr)smem + kPairBiasAt + 16 * g);
 
     for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         // ---- inputs, gathered through the list
@@ -156,9 +203,12 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(pos[c][k]));
         }
-        // previous tile: every wave must be done with the ring before it is refilled
-        __builtin_amdgcn_s_barrier();
-        wt.prologue();
+        // previous tile: every wave must be done with the ring before it is refilled (without a trunk the barrier that opens
+        // the first latent iteration is that barrier)
+        if constexpr (TRUNK) {
+            __builtin_amdgcn_s_barrier();
+            wt.prologue();
+        }
 
         half8 pe_h[2][NCT], pe_l[2][NCT];
         // (an opaque copy keeps the encoder's selectors inside the tile, as in styled_rays_multi_kernel)
@@ -170,7 +220,7 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
             encode_point<SPLIT, SPLIT>(pos[c], g_enc, h2, l2, nullptr);
             pe_h[0][c] = h2[0], pe_h[1][c] = h2[1], pe_l[0][c] = l2[0], pe_l[1][c] = l2[1];
         }
-        wt.start();
+        if constexpr (TRUNK) wt.start();
 
         half8 Xh[8][NCT], Xl[8][NCT], Yh[8][NCT], Yl[8][NCT];
         auto to_Y = [&](auto rt_, auto c_, auto h_, const float4v& acc) {
@@ -181,6 +231,7 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
             constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value;
             store_act<C, rt, decltype(h_)::value>(acc, Xh[rt / 2][c], Xl[rt / 2][c]);
         };
+        if constexpr (TRUNK) {
         // ---- NeRF trunk (models.py:95-101), once per tile
         dense_layer<C, L::frag0(0), 2, 16, L::bias0(0)>(wt, nerf_bias, pe_h, pe_l, to_Y);
         dense_layer<C, L::frag0(1), 8, 16, L::bias0(1)>(wt, nerf_bias, Yh, Yl, to_X);
@@ -202,17 +253,21 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
         dense_layer<C, L::frag0(8), 8, 1, L::bias0(8)>(wt, nerf_bias, Xh, Xl, [&](auto, auto, auto h_, const float4v& acc) {
             if constexpr (decltype(h_)::value == 0) asm volatile("" ::"v"(acc[0]));
         });
-        // base_remap: streams to slab region B as it is produced, where it stays for the K iterations
+        // base_remap: streams to slab region B (to the tile's tile of the plane) as it is produced, where it stays for the K
+        // iterations (for the caller)
         {
             half8 Th[NCT], Tl[NCT];
             dense_layer<C, L::frag0(9), 8, 16, L::bias0(9)>(wt, nerf_bias, Xh, Xl, [&](auto rt_, auto c_, auto h_, const float4v& acc) {
                 constexpr int rt = decltype(rt_)::value, c = decltype(c_)::value, hf = decltype(h_)::value;
                 store_act<C, rt, hf>(acc, Th[c], Tl[c]);
-                if constexpr ((rt & 1) && hf == 1) stash_store<C>(slab + a.stash2_delta, rt / 2, c, Th[c], Tl[c]);
+                if constexpr ((rt & 1) && hf == 1) stash_store<C>(remap_at(tile), rt / 2, c, Th[c], Tl[c]);
             });
         }
+        }   // TRUNK
 
-        if constexpr (FOLD) {
+        if constexpr (!STYLE) {
+            // the trunk producer: next tile
+        } else if constexpr (FOLD) {
             for (int k = 0; k < a.K; ++k) {
                 // every wave must be done with the previous stream, and with the previous latent's bias table
                 __builtin_amdgcn_s_barrier();
@@ -221,14 +276,14 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
 #pragma unroll
                     for (int j = 0; j < kStylePairBiasBytes / (C::NWAVES * 1024); ++j)
                         __builtin_amdgcn_global_load_lds(TGTC_GPTR(table + (j * C::NWAVES + wave) * 1024 + lane * 16),
-                                                         TGTC_LPTR(smem + kRingBytes + kNerfBiasBytes + (j * C::NWAVES + wave) * 1024),
+                                                         TGTC_LPTR(smem + kPairBiasAt + (j * C::NWAVES + wave) * 1024),
                                                          16, 0, 0);
                 }
                 ws.prologue();
                 ws.start();
                 concat_mlp_folded<C, Map::F_CONCAT, 0>(ws, pair_bias, pe_h, pe_l, Xh, Xl, Yh, Yl);
                 // ---- style layer 0 on [remap (slab B -> X) | concat_features (Y) | pe]; outputs stream to slab A
-                stash_load<C>(slab + a.stash2_delta, Xh, Xl);
+                stash_load<C>(remap_at(tile), Xh, Xl);
                 {
                     half8 Bh[18][NCT], Bl[18][NCT];
 #pragma unroll
@@ -292,7 +347,7 @@ __global__ void __launch_bounds__(C::NWAVES * 64, C::NWAVES / 4) styled_rays_spa
             // ---- concat MLP -> Y
             concat_mlp<C, Map::F_CONCAT, 0>(ws, pair_bias, pe_h, pe_l, z_h, z_l, Xh, Xl, Yh, Yl);
             // ---- style layer 0 on [remap (slab B -> X) | concat_features (Y) | pe | mean z]; outputs stream to slab A
-            stash_load<C>(slab + a.stash2_delta, Xh, Xl);
+            stash_load<C>(remap_at(tile), Xh, Xl);
             {
                 half8 Bh[19][NCT], Bl[19][NCT];
 #pragma unroll
@@ -334,11 +389,26 @@ using CfgExact = MlpCfg<8, 1, true, 4>;
 // Each of the four instances (fp16x3 / fp16, scattered / compact) is compiled in a translation unit of its own -- this
 // source as it is, with -DTGTC_TU_FP16_ONLY, -DTGTC_TU_COMPACT or both -- so that the kernels build in parallel.  The four
 // folded instances likewise, with -DTGTC_TU_FOLD in front of the same three combinations and of none.
-template <class C, bool COMPACT, bool FOLD = false>
+// The six plane instances (producer: fp16x3 / fp16; consumer: those x unfolded / folded) likewise, with -DTGTC_TU_PLANE=1
+// (kPlaneBuild) or =2 (kPlaneRead) in front of -DTGTC_TU_FP16_ONLY and -DTGTC_TU_FOLD.
+template <class C, bool COMPACT, bool FOLD = false, int PLANE = kPlaneNone>
 void launch_styled_rays_sparse(unsigned grid, const StyledSparseArgs& a, hipStream_t st) {
-    styled_rays_sparse_kernel<C, COMPACT, FOLD><<<grid, C::NWAVES * 64, 0, st>>>(a);
+    styled_rays_sparse_kernel<C, COMPACT, FOLD, PLANE><<<grid, C::NWAVES * 64, 0, st>>>(a);
 }
-#if defined(TGTC_TU_FOLD)
+#if defined(TGTC_TU_PLANE)
+#ifdef TGTC_TU_FP16_ONLY
+using CfgPlane = CfgFast;
+#else
+using CfgPlane = CfgExact;
+#endif
+#ifdef TGTC_TU_FOLD
+constexpr bool kPlaneFold = true;
+#else
+constexpr bool kPlaneFold = false;
+#endif
+template void launch_styled_rays_sparse<CfgPlane, true, kPlaneFold, TGTC_TU_PLANE>(unsigned, const StyledSparseArgs&, hipStream_t);
+}  // namespace tgtc
+#elif defined(TGTC_TU_FOLD)
 #ifdef TGTC_TU_FP16_ONLY
 using CfgFold = CfgFast;
 #else
@@ -368,6 +438,12 @@ extern template void launch_styled_rays_sparse<CfgExact, false, true>(unsigned, 
 extern template void launch_styled_rays_sparse<CfgFast, false, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 extern template void launch_styled_rays_sparse<CfgExact, true, true>(unsigned, const StyledSparseArgs&, hipStream_t);
 extern template void launch_styled_rays_sparse<CfgFast, true, true>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, true, false, kPlaneBuild>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, true, false, kPlaneBuild>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, true, false, kPlaneRead>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, true, false, kPlaneRead>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgExact, true, true, kPlaneRead>(unsigned, const StyledSparseArgs&, hipStream_t);
+extern template void launch_styled_rays_sparse<CfgFast, true, true, kPlaneRead>(unsigned, const StyledSparseArgs&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------ compaction
 // The plane of M weights is cut into kCompactParts contiguous ranges of `span` samples (a multiple of the block size).
@@ -606,5 +682,55 @@ int styled_restyle_live_folded_impl(const tgtc_net* nerf, const tgtc_net* style,
     return TGTC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ trunk plane
+// tgtc_geometry_trunk / tgtc_restyle_rays_trunk[_folded] (render.hip; count >= 1, sizes, precisions and handle kinds are
+// checked there).  The producer needs no style handle and the consumers no NeRF handle.
+
+// plane[tile] = base_remap's operand fragments of list entries [tile * S, (tile + 1) * S); grid: the tiles, at most one
+// workgroup per CU
+int styled_trunk_plane_impl(const tgtc_net* nerf, const double* rays_o, const double* rays_d, int64_t R, int N,
+                            const uint32_t* live, const float* ts_live, int64_t count, void* plane, hipStream_t st) {
+    int cus = 0;
+    if (const int rc = cu_count(cus)) return rc;
+    StyledSparseArgs a{};
+    a.nerf_bias = nerf->dev, a.nerf_stream = nerf->dev + nerf->bias_bytes;
+    a.M = count, a.R = R, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.live = live, a.ts_live = ts_live;
+    a.count = (unsigned)count, a.plane = static_cast<char*>(plane);
+    if (nerf->precision == TGTC_PREC_FP16) {
+        const long long tiles = (count + CfgFast::SAMPLES_PER_WG - 1) / CfgFast::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgFast, true, false, kPlaneBuild>((unsigned)(tiles < cus ? tiles : cus), a, st);
+    } else {
+        const long long tiles = (count + CfgExact::SAMPLES_PER_WG - 1) / CfgExact::SAMPLES_PER_WG;
+        launch_styled_rays_sparse<CfgExact, true, false, kPlaneBuild>((unsigned)(tiles < cus ? tiles : cus), a, st);
+    }
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+// rgb_live[k, i] from the plane: `folded` == nullptr takes z [K,R,32] and the handle's streams, otherwise the K bias tables
+// and the streams packed without the latent k-steps.  The plane is only read.
+int styled_restyle_plane_impl(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
+                              const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
+                              int64_t count, const void* plane, float* rgb_live, hipStream_t st) {
+    StyledSparseArgs a{};
+    a.pair_bias = style->dev, a.folded = static_cast<const char*>(folded);
+    a.concat_stream = style->dev + (folded ? style->fold_stream_off : style->bias_bytes);
+    a.style_stream = style->dev + (folded ? style->fold_stream2_off : style->stream2_off);
+    a.stash = style->dev + style->stash_off;
+    a.M = count, a.R = R, a.N = N, a.K = K;
+    a.rays_o = rays_o, a.rays_d = rays_d, a.z = z, a.live = live, a.ts_live = ts_live, a.count = (unsigned)count, a.rgb = rgb_live;
+    a.plane = static_cast<char*>(const_cast<void*>(plane));
+    const bool fast = style->precision == TGTC_PREC_FP16;
+    const int per_wg = fast ? CfgFast::SAMPLES_PER_WG : CfgExact::SAMPLES_PER_WG;
+    const long long tiles = (count + per_wg - 1) / per_wg;
+    const unsigned grid = (unsigned)(tiles < style->n_wg ? tiles : style->n_wg);
+    if (fast && folded) launch_styled_rays_sparse<CfgFast, true, true, kPlaneRead>(grid, a, st);
+    else if (fast) launch_styled_rays_sparse<CfgFast, true, false, kPlaneRead>(grid, a, st);
+    else if (folded) launch_styled_rays_sparse<CfgExact, true, true, kPlaneRead>(grid, a, st);
+    else launch_styled_rays_sparse<CfgExact, true, false, kPlaneRead>(grid, a, st);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
 }  // namespace tgtc
-#endif  // TGTC_TU_FOLD || TGTC_TU_FP16_ONLY || TGTC_TU_COMPACT
+#endif  // TGTC_TU_PLANE || TGTC_TU_FOLD || TGTC_TU_FP16_ONLY || TGTC_TU_COMPACT

@@ -43,6 +43,11 @@ int styled_forward_list_folded_impl(const tgtc_net* nerf, const tgtc_net* style,
 int styled_restyle_live_folded_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
                                     const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
                                     int64_t count, float* rgb_live, hipStream_t st);
+int styled_trunk_plane_impl(const tgtc_net* nerf, const double* rays_o, const double* rays_d, int64_t R, int N,
+                            const uint32_t* live, const float* ts_live, int64_t count, void* plane, hipStream_t st);
+int styled_restyle_plane_impl(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
+                              const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
+                              int64_t count, const void* plane, float* rgb_live, hipStream_t st);
 int launch_composite_live(const uint32_t* ray_start, const uint32_t* live, const float* w_live, const float* rgb_live, int64_t R,
                           int N, int K, int64_t count, float* rgb_exp, hipStream_t st);
 int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w_f, const float* t_fine, int64_t R, int N,
@@ -696,4 +701,105 @@ extern "C" int tgtc_restyle_rays_folded(const tgtc_net* fine, const tgtc_net* st
     // 3. the depth image
     if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
     return TGTC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ restyle from a trunk plane
+// The last ray-only piece of a restyle -- the fine NeRF trunk, 556 800 of the 556 800 + K x 950 112 multiply-accumulates per
+// live sample -- kept beside the cache: base_remap's operand fragments of every tile of the cached list in a caller-owned
+// plane (tgtc_geometry_trunk), and the restyle from it, which runs the style networks alone and takes no NeRF handle.
+
+extern "C" size_t tgtc_geometry_trunk_bytes(int precision, int64_t count) {
+    if (count <= 0 || (precision != TGTC_PREC_FP16X3 && precision != TGTC_PREC_FP16)) return 0;
+    const int64_t per_tile = precision == TGTC_PREC_FP16 ? 256 : 128;   // SAMPLES_PER_WG of the style kernels
+    return (size_t)((count + per_tile - 1) / per_tile) * (size_t)131072;
+}
+
+extern "C" int tgtc_geometry_trunk(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
+                                   int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
+                                   size_t trunk_bytes, void* stream) {
+    TGTC_REQUIRE(R >= 0 && count >= 0, "geometry_trunk: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt || R == 0, "geometry_trunk: count %lld exceeds the %lld samples", (long long)count,
+                 (long long)(R * nt));
+    TGTC_REQUIRE(fine, "geometry_trunk: null handle");
+    TGTC_REQUIRE(fine->kind == 0, "geometry_trunk: fine must be a NeRF handle");
+    if (fine->precision != TGTC_PREC_FP16X3 && fine->precision != TGTC_PREC_FP16)
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk: the style kernels are built for fp16x3 and fp16 handles only");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && cache && (trunk || count == 0), "geometry_trunk: null pointer");
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "geometry_trunk: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    const size_t need = tgtc_geometry_trunk_bytes(fine->precision, count);
+    TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk: plane of %zu bytes, need %zu", trunk_bytes, need);
+    if (count == 0) return TGTC_OK;
+    return styled_trunk_plane_impl(fine, rays_o, rays_d, R, nt, gc.live, gc.ts_live, count, trunk, as_stream(stream));
+}
+
+// tgtc_restyle_rays / tgtc_restyle_rays_folded with the trunk read from the plane: the same workspaces, the same compositing
+// launch and depth copy behind another style launch.
+static int restyle_rays_trunk(const char* who, bool fold, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                              const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
+                              int64_t count, const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
+                              float* rgb_fine, float* t_fine, void* stream) {
+    TGTC_REQUIRE(K >= 1, "%s: need K >= 1 latents (got %d)", who, K);
+    TGTC_REQUIRE(R >= 0 && count >= 0, "%s: bad argument", who);
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31)) return fail(TGTC_ERR_UNSUPPORTED, "%s: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)", who);
+    TGTC_REQUIRE(count <= R * nt || R == 0, "%s: count %lld exceeds the %lld samples", who, (long long)count, (long long)(R * nt));
+    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: K x count >= 2^31 (fewer latents per call)", who);
+    TGTC_REQUIRE(style, "%s: null handle", who);
+    TGTC_REQUIRE(style->kind == 1, "%s: style must be a style handle", who);
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0) && (trunk || count == 0),
+                 "%s: null pointer", who);
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "%s: cache of %zu bytes, need %zu", who, cache_bytes, gc.total);
+    const size_t need_plane = tgtc_geometry_trunk_bytes(style->precision, count);
+    TGTC_REQUIRE(trunk_bytes >= need_plane, "%s: plane of %zu bytes, need %zu", who, trunk_bytes, need_plane);
+    const size_t need = fold ? tgtc_restyle_folded_workspace_bytes(count, K) : tgtc_restyle_workspace_bytes(count, K);
+    TGTC_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, need %zu", who, workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    float* rgb_live = static_cast<float*>(workspace);
+    int rc;
+    // 1. (the K bias tables, then) concat MLP + style MLP over the cached list, base_remap from the plane (nothing to launch
+    //    for an empty list)
+    if (count > 0) {
+        float* folded = nullptr;
+        if (fold) {
+            folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
+            rc = style_fold_latents_impl(style, z, K, folded, st);
+            if (rc) return rc;
+        }
+        rc = styled_restyle_plane_impl(style, rays_o, rays_d, z, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
+        if (rc) return rc;
+    }
+    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
+    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
+    if (rc) return rc;
+    // 3. the depth image
+    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_restyle_rays_trunk(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z, int K,
+                                       int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
+                                       const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
+                                       float* rgb_fine, float* t_fine, void* stream) {
+    return restyle_rays_trunk("restyle_rays_trunk", false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes,
+                              count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+}
+
+extern "C" int tgtc_restyle_rays_trunk_folded(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
+                                              int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
+                                              int64_t count, const void* trunk, size_t trunk_bytes, void* workspace,
+                                              size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream) {
+    return restyle_rays_trunk("restyle_rays_trunk_folded", true, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
+                              cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }

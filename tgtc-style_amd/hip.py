@@ -75,7 +75,7 @@ _RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_flo
              "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
              "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t,
              "tgtc_style_folded_bytes": c_size_t, "tgtc_render_styled_sparse_folded_workspace_bytes": c_size_t,
-             "tgtc_restyle_folded_workspace_bytes": c_size_t}
+             "tgtc_restyle_folded_workspace_bytes": c_size_t, "tgtc_geometry_trunk_bytes": c_size_t}
 _OPTIONAL = {
     "tgtc_style_create": [ctypes.POINTER(Linear), c_int, ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],
     "tgtc_concat_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
@@ -112,6 +112,13 @@ _OPTIONAL = {
     "tgtc_restyle_folded_workspace_bytes": [c_int64, c_int],
     "tgtc_restyle_rays_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
                                  c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_geometry_trunk_bytes": [c_int, c_int64],
+    "tgtc_geometry_trunk": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p, c_size_t,
+                            c_void_p],
+    "tgtc_restyle_rays_trunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64,
+                                c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_restyle_rays_trunk_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
+                                       c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -19,13 +19,20 @@ class GeometryCache:
     """The ray-only half of a culled stylised render (tgtc_geometry_build + tgtc_geometry_pack): one flat uint8 buffer in the
     layout include/tgtc_hip.h documents -- a 256-byte header, t [R], ray_start [R+1], live / ts_live / w_live [count], every
     plane rounded up to 256 bytes -- plus the metadata a restyle is checked against.  `key` is any string the caller uses
-    to tell caches apart (None: unchecked)."""
+    to tell caches apart (None: unchecked).
+
+    `trunk` (None unless asked for: RayRenderer.build_trunk) is the trunk plane of tgtc_geometry_trunk, a uint8 device tensor
+    of trunk_nbytes(trunk_precision, count) bytes -- base_remap of every list entry as the style kernels' operand fragments,
+    1 KiB per live sample in fp16x3, 512 B in fp16 -- from which `restyle` runs without any NeRF network.  It is valid only
+    for this list and for style pairs packed in `trunk_precision` (a name of hip.PRECISIONS)."""
     MAGIC, VERSION = 0x43475447, 1
+    TRUNK_TILE_BYTES = 131072
 
     def __init__(self, buffer, R, N, count, min_weight, key=None, n_coarse=None, n_fine=None):
         self.buffer, self.R, self.N, self.count = buffer, int(R), int(N), int(count)
         self.min_weight, self.key = float(min_weight), key
         self.n_coarse, self.n_fine = n_coarse, n_fine
+        self.trunk = self.trunk_precision = None
         if buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.numel() < self.nbytes(self.R, self.count):
             raise ValueError("GeometryCache: the buffer must be uint8 [>= %d] for R = %d, count = %d"
                              % (self.nbytes(self.R, self.count), self.R, self.count))
@@ -44,6 +51,29 @@ class GeometryCache:
     def nbytes(cls, R, count):
         return cls._planes(R, count)[1]
 
+    @classmethod
+    def trunk_nbytes(cls, precision, count):
+        """tgtc_geometry_trunk_bytes: one 128 KiB tile per 128 (fp16x3) / 256 (fp16) list entries; 0 for an empty list or a
+        precision the style kernels are not built for.  `precision`: a name of hip.PRECISIONS or the library's enum."""
+        per_tile = {hip.PREC_FP16X3: 128, hip.PREC_FP16: 256}.get(hip.PRECISIONS.get(precision, precision))
+        if per_tile is None or count <= 0:
+            return 0
+        return (count + per_tile - 1) // per_tile * cls.TRUNK_TILE_BYTES
+
+    def attach_trunk(self, trunk, precision):
+        """Take `trunk` as this cache's plane.  ValueError unless it is uint8 [trunk_nbytes(precision, count)]."""
+        if precision not in ("fp16x3", "fp16"):
+            raise ValueError("GeometryCache: a trunk plane exists in fp16x3 and fp16 only (got %r)" % (precision,))
+        need = self.trunk_nbytes(precision, self.count)
+        if trunk.dtype != torch.uint8 or trunk.dim() != 1 or trunk.numel() != need:
+            raise ValueError("GeometryCache: the %s trunk plane of %d list entries is uint8 [%d], got %s %s"
+                             % (precision, self.count, need, trunk.dtype, list(trunk.shape)))
+        self.trunk, self.trunk_precision = trunk, precision
+
+    def drop_trunk(self):
+        """Release the plane; the cache restyles through the fine NeRF handle again."""
+        self.trunk = self.trunk_precision = None
+
     def _view(self, name, dtype):
         off, words = self._planes(self.R, self.count)[0][name]
         return self.buffer[off:off + 4 * words].view(dtype)
@@ -55,15 +85,23 @@ class GeometryCache:
     ts_live = property(lambda self: self._view("ts_live", torch.float32))
     w_live = property(lambda self: self._view("w_live", torch.float32))
 
-    def save(self, path):
-        """One file: the buffer (moved to the host) and the metadata."""
-        torch.save({"buffer": self.buffer.detach().cpu(), "R": self.R, "N": self.N, "count": self.count,
-                    "min_weight": self.min_weight, "key": self.key, "n_coarse": self.n_coarse, "n_fine": self.n_fine}, path)
+    def save(self, path, with_trunk=False):
+        """One file: the buffer (moved to the host) and the metadata.  The trunk plane is left out unless with_trunk (it is
+        some 80 times the buffer, and build_trunk makes it again from a loaded cache in about one trunk pass); a file saved
+        without it is the file of a cache that never had one."""
+        d = {"buffer": self.buffer.detach().cpu(), "R": self.R, "N": self.N, "count": self.count,
+             "min_weight": self.min_weight, "key": self.key, "n_coarse": self.n_coarse, "n_fine": self.n_fine}
+        if with_trunk:
+            if self.trunk is None:
+                raise ValueError("GeometryCache.save: with_trunk, but the cache carries no trunk plane")
+            d["trunk"], d["trunk_precision"] = self.trunk.detach().cpu(), self.trunk_precision
+        torch.save(d, path)
 
     @classmethod
     def load(cls, path, device):
-        """The cache of `save` on `device`.  ValueError if the header in the buffer contradicts the metadata or the list
-        leaves the sample range (a damaged file must not reach the kernels)."""
+        """The cache of `save` on `device`, with its trunk plane if the file has one.  ValueError if the header in the buffer
+        contradicts the metadata, the list leaves the sample range or the plane's size contradicts trunk_nbytes (a damaged
+        file must not reach the kernels)."""
         d = torch.load(path, map_location="cpu")
         c = cls(d["buffer"].contiguous(), d["R"], d["N"], d["count"], d["min_weight"], d["key"], d["n_coarse"], d["n_fine"])
         want = [cls.MAGIC, cls.VERSION, c.R & 0xffffffff, c.R >> 32, c.N, c.count,
@@ -74,6 +112,9 @@ class GeometryCache:
         if c.count and not (0 <= int(c.live.min()) and int(c.live.max()) < c.R * c.N and int(c.ray_start[-1]) == c.count
                             and int(c.ray_start.min()) >= 0 and int(c.ray_start.max()) <= c.count):
             raise ValueError("GeometryCache.load: %s: the list leaves the sample range" % path)
+        if d.get("trunk") is not None:
+            c.attach_trunk(d["trunk"].contiguous(), d.get("trunk_precision"))
+            c.trunk = c.trunk.to(device)
         c.buffer = c.buffer.to(device)
         return c
 
@@ -258,10 +299,12 @@ class RayRenderer:
                                                     ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
         return {"rgb": rgb, "t": t}
 
-    def build_geometry(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, min_weight=0., key=None):
+    def build_geometry(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, min_weight=0., key=None,
+                       keep_trunk=False):
         """Everything of `render_latents(..., min_weight=min_weight)` that depends on the rays alone -- coarse pass, fine
         depths, sigma pass, weights, compaction -- as a GeometryCache (about 12 bytes per live sample + 8 per ray).  The
-        host reads the live count once here (one synchronisation per build); `restyle` has none."""
+        host reads the live count once here (one synchronisation per build); `restyle` has none.
+        keep_trunk: also `build_trunk` the cache (1 KiB per live sample in fp16x3, 512 B in fp16)."""
         hip.require_gpu(rays_o, rays_d)
         lib = hip.load()
         if n_fine <= 0:
@@ -287,20 +330,51 @@ class RayRenderer:
         buf = torch.zeros(lib.tgtc_geometry_cache_bytes(R, count), dtype=torch.uint8, device=dev)   # padding bytes: 0 in the file
         hip.check(lib.tgtc_geometry_pack(hip.ptr(ws), R, n_coarse, n_fine, min_weight, count, hip.ptr(buf), buf.numel(),
                                          hip.stream()))
-        return GeometryCache(buf, R, n_coarse + n_fine, count, min_weight, key, n_coarse, n_fine)
+        cache = GeometryCache(buf, R, n_coarse + n_fine, count, min_weight, key, n_coarse, n_fine)
+        return self.build_trunk(cache, rays_o, rays_d) if keep_trunk else cache
 
-    def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None):
+    def build_trunk(self, cache, rays_o, rays_d):
+        """Give `cache` its trunk plane: the fine NeRF trunk once over the cached list (tgtc_geometry_trunk; no coarse pass,
+        no sigma pass, no synchronisation), base_remap kept as the style kernels' operand fragments in the fine handle's
+        precision.  `restyle` then needs no NeRF network for this cache.  rays_o / rays_d must be the rays of the build.
+        Returns the cache."""
+        hip.require_gpu(rays_o, rays_d, cache.buffer)
+        lib = hip.load()
+        if rays_o.shape[0] != cache.R:
+            raise ValueError("build_trunk: %d rays, the cache holds %d" % (rays_o.shape[0], cache.R))
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        fine = self.fine.packed()
+        plane = torch.empty(cache.trunk_nbytes(fine.precision, cache.count), dtype=torch.uint8, device=rays_o.device)
+        hip.check(lib.tgtc_geometry_trunk(fine.handle, hip.ptr(rays_o), hip.ptr(rays_d), cache.R, cache.n_coarse, cache.n_fine,
+                                          hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(plane), plane.numel(),
+                                          hip.stream()))
+        cache.attach_trunk(plane, fine.precision)
+        return cache
+
+    def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None, use_trunk=None):
         """The rays of `cache` under K latent sets: zs float [K,R,32] -> dict rgb [K,R,3], t [R], live (the cache's count, a
         host int).  One launch of the compact indexed style kernel over the cached list and one compositing launch; the
         bits of `render_latents(..., min_weight=cache.min_weight)`.  rays_o / rays_d must be the rays the cache was built
         from (it stores depths, not positions).  ValueError before any launch if R, a given n_coarse + n_fine or a given
         `key` does not match the cache.
         zs float [K,32]: K latents that are the same for every ray, through tgtc_restyle_rays_folded (see render_latents);
-        the same cache serves both forms."""
-        hip.require_gpu(rays_o, rays_d, zs, cache.buffer)
-        lib = hip.load()
+        the same cache serves both forms.
+        use_trunk: None takes the cache's trunk plane iff it carries one (`build_trunk`), False ignores it, True insists
+        (ValueError without one).  From the plane the call is tgtc_restyle_rays_trunk[_folded]: the style networks alone, the
+        same bits, and no NeRF network -- a renderer built with coarse=None, fine=None can make it.  ValueError before any
+        launch if the plane was built in another precision than the style pair's."""
         if self.style is None:
             raise ValueError("restyle needs a style pair")
+        if use_trunk is None:
+            use_trunk = cache.trunk is not None
+        elif use_trunk and cache.trunk is None:
+            raise ValueError("restyle: use_trunk=True, but the cache carries no trunk plane (build_trunk)")
+        if use_trunk and cache.trunk_precision != self.style.packed().precision:
+            raise ValueError("restyle: the trunk plane was built in %s, the style pair is packed in %s"
+                             % (cache.trunk_precision, self.style.packed().precision))
+        hip.require_gpu(rays_o, rays_d, zs, cache.buffer, cache.trunk if use_trunk else None)
+        lib = hip.load()
         R = rays_o.shape[0]
         if R != cache.R:
             raise ValueError("restyle: %d rays, the cache holds %d" % (R, cache.R))
@@ -327,6 +401,12 @@ class RayRenderer:
         ws = self._ws_restyle
         rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
+        if use_trunk:
+            call = lib.tgtc_restyle_rays_trunk_folded if folded else lib.tgtc_restyle_rays_trunk
+            hip.check(call(self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R, cache.n_coarse,
+                           cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(cache.trunk),
+                           cache.trunk.numel(), hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
+            return {"rgb": rgb, "t": t, "live": cache.count}
         call = lib.tgtc_restyle_rays_folded if folded else lib.tgtc_restyle_rays
         hip.check(call(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R,
                        cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(ws),
