@@ -149,6 +149,16 @@ int tgtc_sample_fine(const double* rays_o, const double* rays_d, const float* ts
 #define TGTC_PATH_CHAIN 2
 int tgtc_render_path(int request, int prec_coarse, int prec_fine, int prec_style, int n_coarse, int n_fine, int want_coarse);
 
+/* The first half of a ray kernel on its own -- coarse depths -> coarse sigma -> weights -> inverse-CDF fine sampling + merge --
+ * as the depths-only instance of the plain ray kernel computes it (the one the stylised chain, the multi-latent, culled and
+ * restyle renders take their depths from): ts_out float [R, n_coarse + n_fine], ascending, the depths a ray kernel built
+ * for this coarse handle evaluates its fine pass at.  jitter: float [R,n_coarse] or NULL.  One launch, no workspace.
+ * TGTC_ERR_UNSUPPORTED where no plain ray kernel is built for (coarse precision, n_coarse, n_fine) -- the shape rule of
+ * TGTC_PATH_RAY_KERNEL above -- or the coarse handle is TGTC_PREC_FP16_FP6 (no depths-only instance exists for it);
+ * null pointers or a handle that is not a NeRF handle -> TGTC_ERR_ARG;  R == 0 -> TGTC_OK without a launch. */
+int tgtc_render_depths(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
+                       int n_fine, float near_, float far_, const float* jitter, float* ts_out, void* stream);
+
 /* ------------------------------------------------------------------ fused plain render (cal_geometry chain)
  * rendering.py:27-51: coarse sample -> NeRF(coarse) -> composite -> fine sample -> NeRF(fine) -> composite.
  * jitter: float [R,n_coarse] or NULL.  Outputs: rgb float [R,3], depth float [R]; optional coarse outputs.

@@ -125,7 +125,7 @@ def vae_encode(sd, x, depth=4):
 
 
 def render_plain(sd_coarse, sd_fine, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., dtype=torch.float32, dtype_fine=None,
-                 ts_fine=None):
+                 ts_fine=None, jitter=None):
     """The cal_geometry chain, one chunk.  rendering.py:27-51 (perturb=False, det fine sampling).
 
     Returns dict with coarse and fine rgb_exp / t_exp / weights plus the fine t values.
@@ -133,9 +133,10 @@ def render_plain(sd_coarse, sd_fine, rays_o, rays_d, n_coarse, n_fine, near=0., 
     conditioning probes of the whole-frame tests (tests/conditioning.py), not the reference's arithmetic.
     ts_fine [R, n_coarse + n_fine] (optional): evaluate the fine network and its compositing at THESE merged depths instead
     of the ones sampled here (conditional parity of tests/conditioning.py: the sampler's branch taken as given).
+    jitter [R, n_coarse] (optional; the reference's cal_geometry never jitters): stratified coarse depths, as render_styled.
     """
     dtype_fine = dtype_fine or dtype
-    pts, ts = raymarch.sample_coarse(rays_o, rays_d, n_coarse, near, far, dtype=dtype)
+    pts, ts = raymarch.sample_coarse(rays_o, rays_d, n_coarse, near, far, jitter, dtype=dtype)
     dirs = rays_d[:, None, :].expand(-1, n_coarse, -1)
     c = style_nerf(sd_coarse, pts, dirs, dtype=dtype)
     rgb_c, t_c, w_c = raymarch.composite(c["rgb"], c["sigma"], ts)

@@ -179,6 +179,23 @@ extern "C" int tgtc_render_path(int request, int prec_coarse, int prec_fine, int
     return request;
 }
 
+// The depths-only instance of the plain ray kernel as an entry of its own: what the stylised chain, the multi-latent, the
+// culled and the restyle renders launch internally, and what lets a test hold a ray kernel's pixel against a reference
+// evaluated at the kernel's own fine depths (tests/test_ray_kernel_shapes_gpu.py).
+extern "C" int tgtc_render_depths(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
+                                  int n_fine, float near_, float far_, const float* jitter, float* ts_out, void* stream) {
+    TGTC_REQUIRE(coarse && R >= 0, "render_depths: bad argument");
+    TGTC_REQUIRE(coarse->kind == 0, "render_depths: coarse must be a NeRF handle");
+    if (coarse->precision == TGTC_PREC_FP16_FP6 ||
+        !ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0))
+        return fail(TGTC_ERR_UNSUPPORTED, "render_depths: no depths-only ray kernel for coarse precision %d, %d + %d samples",
+                    coarse->precision, n_coarse, n_fine);
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts_out, "render_depths: null pointer");
+    FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ts_out};
+    return launch_fused_depths(coarse->precision, a, as_stream(stream));
+}
+
 // ---- the two-phase fine pass of the plain chain
 // A fine sample with sigma <= 0 has alpha = 1 - exp(-relu(sigma) delta) = 0 exactly, weight 0 x T = +0, and enters the pixel
 // as acc + 0 x c: for finite colours the image does not need its colour head.  With the live share L of the samples, f the

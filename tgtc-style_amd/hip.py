@@ -63,6 +63,7 @@ _SIGNATURES = {
     "tgtc_sample_fine": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "tgtc_render_workspace_bytes": [c_int64, c_int, c_int],
     "tgtc_render_path": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
+    "tgtc_render_depths": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
     "tgtc_render_rays_plain": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float,
                                c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_image_epilogue": [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p],

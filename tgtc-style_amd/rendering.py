@@ -231,6 +231,24 @@ class RayRenderer:
             out["rgb_coarse"], out["t_coarse"] = rgb_c, t_c
         return out
 
+    def ray_kernel_depths(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None):
+        """The merged fine-pass depths float [R, n_coarse + n_fine] (ascending) a ray kernel built for this renderer's coarse
+        handle evaluates its fine pass at: the depths-only instance of the plain ray kernel (tgtc_render_depths), one launch,
+        no workspace.  ValueError where no such kernel is built (sample counts, or a coarse handle in fp16mx)."""
+        hip.require_gpu(rays_o, rays_d)
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        R = rays_o.shape[0]
+        ts = torch.empty(R, n_coarse + n_fine, device=rays_o.device, dtype=torch.float32)
+        if jitter is not None:
+            jitter = jitter.to(torch.float32).contiguous()
+        rc = hip.load().tgtc_render_depths(self.coarse.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), R, n_coarse, n_fine,
+                                           float(near), float(far), hip.ptr(jitter), hip.ptr(ts), hip.stream())
+        if rc == -2:       # TGTC_ERR_UNSUPPORTED
+            raise ValueError("ray_kernel_depths: no depths-only ray kernel for this coarse precision and these sample counts")
+        hip.check(rc)
+        return ts
+
     def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None, min_weight=None):
         """The same rays under K latent sets in one call: zs float [K,R,32] -> dict rgb [K,R,3], t [R].
 
