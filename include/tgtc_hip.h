@@ -463,6 +463,40 @@ int tgtc_restyle_rays_trunk_folded(const tgtc_net* style, const double* rays_o, 
                                    const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
                                    float* rgb_fine, float* t_fine, void* stream);
 
+/* ------------------------------------------------------------------ restyle from the trunk plane, style networks in fp16mx
+ * tgtc_style_create refuses TGTC_PREC_FP16_FP6: the dense stylised kernels have no room for its third activation set.  The
+ * folded restyle from a trunk plane has -- no NeRF stream, no latent k-step -- so the fp16mx arithmetic of the NeRF nets
+ * (one fp16 product plus two block-scaled e2m3 correction products per 128-deep block, csrc/mlp_mx.h) arrives there as a
+ * SECOND PAIR OF STREAMS on a TGTC_PREC_FP16X3 style handle, behind entry points of its own.  It is a mode the caller asks
+ * for; nothing selects it, and nothing else on the handle changes.
+ *
+ * tgtc_style_enable_mx: packs the handle's 13 equalised layers without their latent k-steps as fp16mx group streams (K groups
+ *   of 7 KiB: Wh x 4, Wl6, Wh6; the encoding k-steps in fp16 hi + lo) and one pair of e2m3 row exponents per output row, chosen
+ *   as tgtc_nerf_create chooses them, into an allocation of its own (about 3 MB) that tgtc_net_destroy frees.  The tables of
+ *   tgtc_style_fold_latents apply unchanged.  `stream` orders the upload; the call returns when it is done.  A second call is a
+ *   no-op (TGTC_OK).  A handle in TGTC_PREC_FP16 -> TGTC_ERR_UNSUPPORTED: its plane has no lo halves to correct from.
+ * tgtc_style_has_mx: 1 once enabled, else 0 (also for NULL and for NeRF handles).
+ * tgtc_style_mx_read (the seam the packing test uses; HOST buffers, synchronous): the packed group streams (both, in stream
+ *   order), the row-exponent table (8192 bytes) and the 13 equalised weight matrices they were packed from ([out,in] row-major,
+ *   concat layers 0..4 then style layers 0..7; 1 020 384 floats).  The three sizes must be exact -> TGTC_ERR_ARG otherwise, with
+ *   the sizes in the message; no mx streams -> TGTC_ERR_UNSUPPORTED.
+ * tgtc_restyle_rays_trunk_folded_mx: the arguments (z float [K,32]), workspace (tgtc_restyle_folded_workspace_bytes), compositing
+ *   launch, depth copy, count == 0 rule and errors of tgtc_restyle_rays_trunk_folded, with the concat MLP and the style MLP run by
+ *   the fp16mx plane consumer (csrc/mlp_style_mx.hip).  The plane is the TGTC_PREC_FP16X3 plane of tgtc_geometry_trunk: its hi
+ *   and lo fragments are the fp16 operand and the source of the e2m3 blocks.  A handle without mx streams ->
+ *   TGTC_ERR_UNSUPPORTED, checked where the handle's kind is.
+ *   Results differ from tgtc_restyle_rays_trunk_folded within the precision's error (1e-3 against float64 per sample, the
+ *   TGTC_PREC_FP16_FP6 bar); t_fine is the same copy.  Deterministic: K latents in one call are the bits of K calls.
+ * Scratch slab: slab region A of the STYLE HANDLE; launches on one style handle must not overlap. */
+int tgtc_style_enable_mx(tgtc_net* style, void* stream);
+int tgtc_style_has_mx(const tgtc_net* style);
+int tgtc_style_mx_read(const tgtc_net* style, void* groups, size_t groups_bytes, void* row_exp, size_t row_exp_bytes, float* weights,
+                       size_t weight_floats);
+int tgtc_restyle_rays_trunk_folded_mx(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z, int K,
+                                      int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
+                                      const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
+                                      float* rgb_fine, float* t_fine, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

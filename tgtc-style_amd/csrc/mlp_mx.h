@@ -63,11 +63,13 @@ struct MxTable {
     int bytes = 0;                 // stream length, chunk padded
 };
 
+// seg_layer: the layer whose first group opens a stream of its own (a second WeightStream segment, chunk aligned); -1: none
 template <int NL>
-constexpr MxTable mx_make_table(const MxShape (&s)[NL], int ring_bytes) {
+constexpr MxTable mx_make_table(const MxShape (&s)[NL], int ring_bytes, int seg_layer = -1) {
     MxTable t;
     int off = 0;
     for (int l = 0; l < NL; ++l) {
+        if (l == seg_layer) off = (off + kChunkBytes - 1) / kChunkBytes * kChunkBytes;
         t.first[l] = t.n;
         for (int rt = 0; rt < s[l].rt; ++rt) {
             const int ng = s[l].nkb + (s[l].npe ? 1 : 0);
@@ -90,6 +92,19 @@ constexpr MxShape kNerfMxShape[12] = {{16, 0, 2}, {16, 2, 0}, {16, 2, 0}, {16, 2
                                       {16, 2, 0}, {16, 2, 0}, {1, 2, 0},  {16, 2, 0}, {8, 2, 1},  {1, 1, 0}};
 inline constexpr MxTable kNerfMxTable = mx_make_table(kNerfMxShape, kRingBytes);
 constexpr int kNerfMxScaleOff = 10240;  // byte offset of the row-exponent table inside the bias region (u16 per row)
+
+// The style pair packed without its latent k-steps (mlp_layouts.h: kConcatFoldKS, kStyleFoldKS), for the fp16mx plane consumer
+// (mlp_style_mx.hip).  One group table over both nets, so that ring offsets run on from the concat stream into the style
+// stream; the style MLP's first group is chunk aligned and its groups are a stream of their own (segment 1).
+//   layer            C0  C1  C2  C3  C4  S0  S1  S2  S3  S4  S5  S6  S7
+//   128-deep blocks   0   2   2   2   2   4   2   2   2   2   2   2   2      S0: [remap | concat_features]
+//   encoding k-steps  2   0   0   0   2   2   0   0   0   2   0   0   0
+constexpr MxShape kStylePairMxShape[13] = {{16, 0, 2}, {16, 2, 0}, {16, 2, 0}, {16, 2, 0}, {16, 2, 2}, {16, 4, 2}, {16, 2, 0},
+                                           {16, 2, 0}, {16, 2, 0}, {16, 2, 2}, {16, 2, 0}, {16, 2, 0}, {1, 2, 0}};
+inline constexpr MxTable kStylePairMxTable = mx_make_table(kStylePairMxShape, kRingBytes, 5);
+constexpr int kStylePairMxStyleOff = kStylePairMxTable.off[kStylePairMxTable.first[5]];   // bytes of the concat stream
+constexpr int kStylePairMxExpBytes = 8192;   // u16 per pair bias table entry (3088), padded to 8 waves x 1 KiB of LDS-DMA
+static_assert(kStylePairMxStyleOff % kChunkBytes == 0, "the style stream starts on a chunk");
 
 // e2m3: 1 sign, 2 exponent (bias 1), 3 mantissa bits; codes are monotone in magnitude
 __host__ __device__ inline float e2m3_value(int code) {

@@ -397,6 +397,10 @@ extern "C" int tgtc_net_destroy(tgtc_net* net) {
         (void)hipHostFree(const_cast<uint64_t*>(net->cull->landed));
         delete net->cull;
     }
+    if (net->mx) {
+        if (net->mx->dev) (void)hipFree(net->mx->dev);
+        delete net->mx;
+    }
     delete net;
     if (e != hipSuccess) return fail(TGTC_ERR_HIP, "net_destroy: hipFree: %s", hipGetErrorString(e));
     return TGTC_OK;

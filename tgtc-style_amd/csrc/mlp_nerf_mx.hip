@@ -9,6 +9,7 @@
 
 #include "mlp_layouts.h"
 #include "mlp_mx.h"
+#include "mlp_mx_pack.h"
 #include "mlp_nerf_mx_chain.h"
 
 namespace tgtc {
@@ -83,16 +84,6 @@ __global__ void __launch_bounds__(512, 2) nerf_mx_kernel(NerfArgs a) {
 
 
 // ------------------------------------------------------------------------------------------------ host
-static int e2m3_encode(float x) {
-    float a = std::fabs(x);
-    if (!(a < 7.5f)) a = 7.5f;
-    // position on the (piecewise linear) code axis, then round to nearest, ties to even code
-    const float q = a < 1.0f ? a * 8.0f : (a < 2.0f ? 8.0f + (a - 1.0f) * 8.0f : (a < 4.0f ? 16.0f + (a - 2.0f) * 4.0f : 24.0f + (a - 4.0f) * 2.0f));
-    int c = (int)std::nearbyint(q);  // default rounding mode: ties to even
-    if (c > 31) c = 31;
-    return c | (std::signbit(x) ? 32 : 0);
-}
-
 int nerf_mx_pack(const tgtc_linear* layers, std::vector<char>& bias_region, std::vector<char>& stream) {
     const std::vector<LayerSpec> specs = nerf_specs(layers);
     const MxTable& T = kNerfMxTable;
@@ -104,104 +95,10 @@ int nerf_mx_pack(const tgtc_linear* layers, std::vector<char>& bias_region, std:
                   "row exponent table must fit behind the biases");
     int qi = 0, b0 = 0;
     for (size_t l = 0; l < specs.size(); ++l) {
-        const LayerSpec& Ls = specs[l];
-        const MxShape sh = kNerfMxShape[l];
-        if (Ls.row_tiles() != sh.rt || qi != T.first[l] || b0 != NerfLayout::bias0((int)l))
+        if (qi != T.first[l] || b0 != NerfLayout::bias0((int)l) ||
+            !mx_pack_layer(specs[l], kNerfMxShape[l], T, qi, b0, stream.data(), rowexp, bias))
             return fail(TGTC_ERR_UNSUPPORTED, "nerf_create: internal fp16+fp6 layout mismatch at layer %zu", l);
-        const Seg* act = nullptr;
-        const Seg* pe = nullptr;
-        for (const Seg& s : Ls.segs) (s.kind == SEG_ACT ? act : pe) = &s;
-        if ((act ? act->ksteps : 0) != 4 * sh.nkb || (pe ? pe->ksteps : 0) != sh.npe)
-            return fail(TGTC_ERR_UNSUPPORTED, "nerf_create: internal fp16+fp6 segment mismatch at layer %zu", l);
-        auto weight = [&](int row, int col) -> float {
-            return (row < Ls.out && col >= 0 && col < Ls.in) ? Ls.W[(size_t)row * Ls.in + col] : 0.0f;
-        };
-        for (int rt = 0; rt < sh.rt; ++rt) {
-            // Block exponents of the two fp6 weight operands of each row, one per row over all activation columns and chosen
-            // independently for Wh6 (the fp16 weights) and Wl6 (their rounding residuals): the exponent of the operand's own
-            // largest magnitude puts the codes in [2,4) (no saturation), one below in [4,8) (finer steps, the few values above
-            // 7.5 saturate); the packer takes whichever leaves the smaller squared error.  (Round 2 tied Wl6 to Wh6's exponent
-            // minus 11, which left the residuals two binades below the top of the code range: tests/probes/emu_mx_e2e.py,
-            // EMU_W_SHIFT=best, median end-to-end error 2.3e-5 -> 7.7e-6.)
-            int EH[16], EL[16];
-            for (int r = 0; r < 16; ++r) {
-                const int row = 16 * rt + r;
-                bias[b0 + 16 * rt + r] = row < Ls.out ? Ls.b[row] : 0.0f;
-                auto best = [&](bool lo) {
-                    float mx = 0.0f;
-                    const int ncol = act ? 128 * sh.nkb : 0;
-                    for (int c = 0; c < ncol; ++c) {
-                        const float w = weight(row, act->col0 + c);
-                        const float hi = (float)(half_t)w;
-                        mx = std::fmax(mx, std::fabs(lo ? w - hi : hi));
-                    }
-                    if (!(mx > 0.0f)) return -14 - (lo ? 11 : 0);
-                    int e = 0;
-                    (void)std::frexp(mx, &e);   // mx = f * 2^e, f in [0.5, 1): the value's exponent is e - 1
-                    e -= 1;
-                    int pick = e - 1;
-                    double err_best = -1.0;
-                    for (int cand = e - 1; cand >= e - 2; --cand) {
-                        if (cand < -126) continue;
-                        const float inv = std::ldexp(1.0f, -cand), sc = std::ldexp(1.0f, cand);
-                        double err = 0.0;
-                        for (int c = 0; c < ncol; ++c) {
-                            const float w = weight(row, act->col0 + c);
-                            const float hi = (float)(half_t)w;
-                            const float v = lo ? w - hi : hi;
-                            const double d = (double)e2m3_value(e2m3_encode(v * inv)) * sc - (double)v;
-                            err += d * d;
-                        }
-                        if (err_best < 0.0 || err < err_best) err_best = err, pick = cand;
-                    }
-                    return pick;
-                };
-                EH[r] = best(false), EL[r] = best(true);
-                rowexp[b0 + 16 * rt + r] = (unsigned short)((EH[r] + 127) | ((EL[r] + 127) << 8));
-            }
-            for (int kb = 0; kb < sh.nkb; ++kb, ++qi) {
-                char* base = stream.data() + T.off[qi];
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int m = lane & 15, g = lane >> 4, row = 16 * rt + m;
-                    unsigned long long bl[3] = {0, 0, 0}, bh[3] = {0, 0, 0};
-                    const float inv_l = std::ldexp(1.0f, -EL[m]);  // Wl6 = e2m3(wl / 2^EL)
-                    const float inv_h = std::ldexp(1.0f, -EH[m]);  // Wh6 = e2m3(wh / 2^EH)
-                    auto put = [](unsigned long long (&b)[3], int i, int code) {
-                        const int bit = 6 * i;
-                        b[bit / 64] |= (unsigned long long)code << (bit % 64);
-                        if (bit % 64 > 58) b[bit / 64 + 1] |= (unsigned long long)code >> (64 - bit % 64);
-                    };
-                    for (int s = 0; s < 4; ++s)
-                        for (int j = 0; j < 8; ++j) {
-                            const float w = weight(row, seg_col(*act, 4 * kb + s, g, j));
-                            const half_t hi = (half_t)w;
-                            std::memcpy(base + s * 1024 + lane * 16 + j * 2, &hi, 2);
-                            put(bl, 8 * s + j, e2m3_encode((w - (float)hi) * inv_l));
-                            put(bh, 8 * s + j, e2m3_encode((float)hi * inv_h));
-                        }
-                    // three 16-byte pieces per lane (mlp_mx.h): [Wl6 dwords 0-3] [Wl6 4-5 | Wh6 0-1] [Wh6 2-5]
-                    std::memcpy(base + 4096 + lane * 16, &bl[0], 16);
-                    std::memcpy(base + 5120 + lane * 16, &bl[2], 8);
-                    std::memcpy(base + 5120 + lane * 16 + 8, &bh[0], 8);
-                    std::memcpy(base + 6144 + lane * 16, &bh[1], 16);
-                }
-            }
-            if (sh.npe) {
-                char* base = stream.data() + T.off[qi];
-                for (int k = 0; k < sh.npe; ++k)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane & 15, g = lane >> 4, row = 16 * rt + m;
-                        for (int j = 0; j < 8; ++j) {
-                            const float w = weight(row, seg_col(*pe, k, g, j));
-                            const half_t hi = (half_t)w, lo = (half_t)(w - (float)hi);
-                            std::memcpy(base + (2 * k) * 1024 + lane * 16 + j * 2, &hi, 2);
-                            std::memcpy(base + (2 * k + 1) * 1024 + lane * 16 + j * 2, &lo, 2);
-                        }
-                    }
-                ++qi;
-            }
-        }
-        b0 += 16 * sh.rt;
+        b0 += 16 * kNerfMxShape[l].rt;
     }
     if (qi != T.n) return fail(TGTC_ERR_UNSUPPORTED, "nerf_create: internal fp16+fp6 group count mismatch");
     return TGTC_OK;

@@ -185,6 +185,16 @@ struct tgtc_cull_state {
     long long culled, dense;         // chain renders that took the two-phase fine pass / the dense one
 };
 
+// What a style handle keeps for its fp16mx streams (tgtc_style_enable_mx, mlp_style.hip): the equalised copy of the 13 linears
+// every stream of the handle was packed from, and -- once enabled -- an allocation of its own
+//   [concat group stream | style group stream (mlp_mx.h, kStylePairMxTable)][row exponents, kStylePairMxExpBytes]
+// read by the fp16mx plane consumer (mlp_style_mx.hip).  Nothing inside tgtc_net::dev moves.
+struct tgtc_style_mx {
+    tgtc::EqualisedNet concat, style;
+    char* dev = nullptr;     // nullptr: not enabled
+    size_t exp_off = 0;      // the row-exponent table behind the streams
+};
+
 // The opaque handle of the C ABI.
 struct tgtc_net {
     int kind;        // 0 = NeRF (StyleNerf), 1 = style pair (concat MLP + style MLP)
@@ -203,4 +213,5 @@ struct tgtc_net {
     // columns [kFoldRows, 32] of the 13 layers (tgtc_style_fold_latents and the folded kernels of mlp_style_sparse.hip)
     size_t fold_stream_off, fold_stream2_off, fold_wz_off;
     tgtc_cull_state* cull;  // NeRF handles only (tgtc_nerf_create)
+    tgtc_style_mx* mx;      // style pairs only (tgtc_style_create)
 };

@@ -15,6 +15,8 @@
 #include "mlp_layouts.h"
 #include "mlp_pack.h"
 #include "mlp_style_chain.h"
+#include "mlp_mx.h"
+#include "mlp_style_mx.h"
 
 namespace tgtc {
 
@@ -560,7 +562,65 @@ extern "C" int tgtc_style_create(const tgtc_linear* concat_layers, int n_concat,
         delete net;
         return fail(TGTC_ERR_HIP, "style_create: hipMemcpy: %s", hipGetErrorString(e));
     }
+    // the equalised copy stays with the handle: tgtc_style_enable_mx packs its streams from it
+    net->mx = new tgtc_style_mx();
+    net->mx->concat = std::move(eqc), net->mx->style = std::move(eqs);
     *out = net;
+    return TGTC_OK;
+}
+
+// The fp16mx pair of streams of an fp16x3 handle (mlp_style_mx.h): the folded layers of the handle's equalised copy as group
+// streams with their row exponents, in an allocation of their own.
+extern "C" int tgtc_style_enable_mx(tgtc_net* style, void* stream) {
+    TGTC_REQUIRE(style && style->kind == 1, "style_enable_mx: style must be a style handle");
+    if (style->precision != TGTC_PREC_FP16X3)
+        return fail(TGTC_ERR_UNSUPPORTED, "style_enable_mx: the fp16mx streams belong to a TGTC_PREC_FP16X3 handle (the plane of an "
+                                          "fp16 handle has no lo halves)");
+    TGTC_REQUIRE(style->mx, "style_enable_mx: the handle was not made by tgtc_style_create");
+    if (style->mx->dev) return TGTC_OK;
+    std::vector<char> groups, row_exp;
+    if (const int rc = style_mx_pack(without_latent(concat_specs(style->mx->concat.lin.data())),
+                                     without_latent(style_specs(style->mx->style.lin.data())), groups, row_exp))
+        return rc;
+    // [group streams][a chunk of padding][row exponents]
+    const size_t exp_off = (groups.size() + kChunkBytes + 255) & ~(size_t)255;
+    std::vector<char> host(exp_off + row_exp.size(), 0);
+    memcpy(host.data(), groups.data(), groups.size());
+    memcpy(host.data() + exp_off, row_exp.data(), row_exp.size());
+    char* dev = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, host.size());
+    if (e != hipSuccess) return fail(TGTC_ERR_HIP, "style_enable_mx: hipMalloc(%zu): %s", host.size(), hipGetErrorString(e));
+    e = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(TGTC_ERR_HIP, "style_enable_mx: upload: %s", hipGetErrorString(e));
+    }
+    style->mx->dev = dev, style->mx->exp_off = exp_off;
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_style_has_mx(const tgtc_net* style) { return style && style->kind == 1 && style->mx && style->mx->dev ? 1 : 0; }
+
+// The seam the packing test uses: what tgtc_style_enable_mx packed, copied back, beside the equalised weights it packed from.
+extern "C" int tgtc_style_mx_read(const tgtc_net* style, void* groups, size_t groups_bytes, void* row_exp, size_t row_exp_bytes,
+                                  float* weights, size_t weight_floats) {
+    TGTC_REQUIRE(style && style->kind == 1, "style_mx_read: style must be a style handle");
+    if (!(style->mx && style->mx->dev)) return fail(TGTC_ERR_UNSUPPORTED, "style_mx_read: the style handle has no fp16mx streams");
+    size_t n = 0;
+    for (const EqualisedNet* eq : {&style->mx->concat, &style->mx->style})
+        for (const std::vector<float>& w : eq->w) n += w.size();
+    TGTC_REQUIRE(groups && row_exp && weights, "style_mx_read: null pointer");
+    TGTC_REQUIRE(groups_bytes == (size_t)kStylePairMxTable.bytes && row_exp_bytes == (size_t)kStylePairMxExpBytes && weight_floats == n,
+                 "style_mx_read: buffers of %zu, %zu bytes and %zu floats, need %d, %d and %zu", groups_bytes, row_exp_bytes,
+                 weight_floats, kStylePairMxTable.bytes, kStylePairMxExpBytes, n);
+    TGTC_HIP_CHECK(hipMemcpy(groups, style->mx->dev, groups_bytes, hipMemcpyDeviceToHost));
+    TGTC_HIP_CHECK(hipMemcpy(row_exp, style->mx->dev + style->mx->exp_off, row_exp_bytes, hipMemcpyDeviceToHost));
+    for (const EqualisedNet* eq : {&style->mx->concat, &style->mx->style})
+        for (const std::vector<float>& w : eq->w) {
+            memcpy(weights, w.data(), w.size() * sizeof(float));
+            weights += w.size();
+        }
     return TGTC_OK;
 }
 

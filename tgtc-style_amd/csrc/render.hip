@@ -5,6 +5,7 @@
 #include "common.h"
 
 #include "mlp_pack.h"
+#include "mlp_style_mx.h"
 #include "render_args.h"
 
 namespace tgtc {
@@ -758,7 +759,7 @@ extern "C" int tgtc_geometry_trunk(const tgtc_net* fine, const double* rays_o, c
 
 // tgtc_restyle_rays / tgtc_restyle_rays_folded with the trunk read from the plane: the same workspaces, the same compositing
 // launch and depth copy behind another style launch.
-static int restyle_rays_trunk(const char* who, bool fold, const tgtc_net* style, const double* rays_o, const double* rays_d,
+static int restyle_rays_trunk(const char* who, bool fold, bool mx, const tgtc_net* style, const double* rays_o, const double* rays_d,
                               const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
                               int64_t count, const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
                               float* rgb_fine, float* t_fine, void* stream) {
@@ -773,6 +774,8 @@ static int restyle_rays_trunk(const char* who, bool fold, const tgtc_net* style,
         return fail(TGTC_ERR_UNSUPPORTED, "%s: K x count >= 2^31 (fewer latents per call)", who);
     TGTC_REQUIRE(style, "%s: null handle", who);
     TGTC_REQUIRE(style->kind == 1, "%s: style must be a style handle", who);
+    if (mx && !(style->mx && style->mx->dev))
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
     if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0) && (trunk || count == 0),
                  "%s: null pointer", who);
@@ -794,7 +797,8 @@ static int restyle_rays_trunk(const char* who, bool fold, const tgtc_net* style,
             rc = style_fold_latents_impl(style, z, K, folded, st);
             if (rc) return rc;
         }
-        rc = styled_restyle_plane_impl(style, rays_o, rays_d, z, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
+        if (mx) rc = styled_restyle_plane_mx_impl(style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
+        else rc = styled_restyle_plane_impl(style, rays_o, rays_d, z, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
         if (rc) return rc;
     }
     // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
@@ -809,7 +813,7 @@ extern "C" int tgtc_restyle_rays_trunk(const tgtc_net* style, const double* rays
                                        int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
                                        const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
                                        float* rgb_fine, float* t_fine, void* stream) {
-    return restyle_rays_trunk("restyle_rays_trunk", false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes,
+    return restyle_rays_trunk("restyle_rays_trunk", false, false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes,
                               count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
@@ -817,6 +821,17 @@ extern "C" int tgtc_restyle_rays_trunk_folded(const tgtc_net* style, const doubl
                                               int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
                                               int64_t count, const void* trunk, size_t trunk_bytes, void* workspace,
                                               size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream) {
-    return restyle_rays_trunk("restyle_rays_trunk_folded", true, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
+    return restyle_rays_trunk("restyle_rays_trunk_folded", true, false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
+                              cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+}
+
+// ... and with the style networks in fp16mx: the folded form on the handle's mx streams (tgtc_style_enable_mx; an fp16x3 handle,
+// so the plane's size is checked as the fp16x3 plane's)
+extern "C" int tgtc_restyle_rays_trunk_folded_mx(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
+                                                 int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                                                 size_t cache_bytes, int64_t count, const void* trunk, size_t trunk_bytes,
+                                                 void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
+                                                 void* stream) {
+    return restyle_rays_trunk("restyle_rays_trunk_folded_mx", true, true, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
                               cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }

@@ -120,6 +120,11 @@ _OPTIONAL = {
                                 c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
     "tgtc_restyle_rays_trunk_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
                                        c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_style_enable_mx": [c_void_p, c_void_p],
+    "tgtc_style_has_mx": [c_void_p],
+    "tgtc_style_mx_read": [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t],
+    "tgtc_restyle_rays_trunk_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
+                                          c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
 }
 
 
@@ -220,6 +225,14 @@ class Net:
     def culled_renders(self):
         """How many of those renders took the two-phase fine pass."""
         return int(load().tgtc_net_culled_renders(self.handle))
+
+    def has_mx(self):
+        """Whether this style pair carries its fp16mx streams (tgtc_style_enable_mx)."""
+        return bool(load().tgtc_style_has_mx(self.handle))
+
+    def enable_mx(self):
+        """Pack the fp16mx streams of an fp16x3 style pair beside its other streams (once; RuntimeError for another handle)."""
+        check(load().tgtc_style_enable_mx(self.handle, stream()))
 
     def __del__(self):
         try:

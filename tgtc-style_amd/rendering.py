@@ -370,7 +370,7 @@ class RayRenderer:
         cache.attach_trunk(plane, fine.precision)
         return cache
 
-    def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None, use_trunk=None):
+    def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None, use_trunk=None, style_precision=None):
         """The rays of `cache` under K latent sets: zs float [K,R,32] -> dict rgb [K,R,3], t [R], live (the cache's count, a
         host int).  One launch of the compact indexed style kernel over the cached list and one compositing launch; the
         bits of `render_latents(..., min_weight=cache.min_weight)`.  rays_o / rays_d must be the rays the cache was built
@@ -381,9 +381,25 @@ class RayRenderer:
         use_trunk: None takes the cache's trunk plane iff it carries one (`build_trunk`), False ignores it, True insists
         (ValueError without one).  From the plane the call is tgtc_restyle_rays_trunk[_folded]: the style networks alone, the
         same bits, and no NeRF network -- a renderer built with coarse=None, fine=None can make it.  ValueError before any
-        launch if the plane was built in another precision than the style pair's."""
+        launch if the plane was built in another precision than the style pair's.
+        style_precision: None runs the style networks in the pair's own precision.  "fp16mx" runs them in fp16mx
+        (tgtc_restyle_rays_trunk_folded_mx: one fp16 product and two block-scaled fp6 corrections instead of three fp16
+        products; 1e-3 of float64 per sample instead of 5e-5) on a second pair of streams the fp16x3 pair packs at the first
+        such call.  That form exists for zs [K,32], a cache with an fp16x3 trunk plane and an fp16x3 style pair only: anything
+        else is a ValueError before any launch.  No default selects it."""
         if self.style is None:
             raise ValueError("restyle needs a style pair")
+        if style_precision not in (None, "fp16mx"):
+            raise ValueError("restyle: style_precision is None or 'fp16mx', got %r" % (style_precision,))
+        mx = style_precision == "fp16mx"
+        if mx:
+            if zs.dim() != 2:
+                raise ValueError("restyle: style_precision='fp16mx' takes frame-constant latents zs [K,32], got %s" % list(zs.shape))
+            if use_trunk is False or cache.trunk is None:
+                raise ValueError("restyle: style_precision='fp16mx' restyles from a trunk plane (build_trunk)")
+            if cache.trunk_precision != "fp16x3" or self.style.packed().precision != "fp16x3":
+                raise ValueError("restyle: style_precision='fp16mx' needs an fp16x3 trunk plane and an fp16x3 style pair (plane %s, "
+                                 "pair %s)" % (cache.trunk_precision, self.style.packed().precision))
         if use_trunk is None:
             use_trunk = cache.trunk is not None
         elif use_trunk and cache.trunk is None:
@@ -419,8 +435,12 @@ class RayRenderer:
         ws = self._ws_restyle
         rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
-        if use_trunk:
+        if mx:
+            self.style.packed().enable_mx()                         # a no-op from the second call on
+            call = lib.tgtc_restyle_rays_trunk_folded_mx
+        elif use_trunk:
             call = lib.tgtc_restyle_rays_trunk_folded if folded else lib.tgtc_restyle_rays_trunk
+        if use_trunk:
             hip.check(call(self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R, cache.n_coarse,
                            cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(cache.trunk),
                            cache.trunk.numel(), hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
