@@ -497,6 +497,33 @@ int tgtc_restyle_rays_trunk_folded_mx(const tgtc_net* style, const double* rays_
                                       const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
                                       float* rgb_fine, float* t_fine, void* stream);
 
+/* ------------------------------------------------------------------ the trunk plane from an fp16mx fine network
+ * tgtc_geometry_trunk refuses a fine handle in TGTC_PREC_FP16_FP6, and stays that way: a plane is read by the style kernels
+ * and exists in their two layouts only.  tgtc_geometry_trunk_mx is the producer for such a handle: it runs the NeRF trunk in
+ * fp16mx (csrc/mlp_trunk_mx.hip: the fp16mx per-sample kernel's layers 0-7, sigma groups and base_remap_layer on the handle's
+ * own group stream and row exponents, one workgroup per 128-entry tile) and writes a TGTC_PREC_FP16X3 PLANE -- base_remap,
+ * ReLU-ed, split into fp16 hi and lo = fp16(v - hi), in the layout above -- which tgtc_restyle_rays_trunk[_folded] and
+ * tgtc_restyle_rays_trunk_folded_mx read with a TGTC_PREC_FP16X3 style handle.  Densities (the cache) and base_remap (the
+ * plane) then come from the same packed network.  It is a mode the caller asks for; nothing selects it.
+ *
+ * tgtc_geometry_trunk_mx: the arguments, checks, check order and count == 0 / R == 0 rules of tgtc_geometry_trunk.  `fine`
+ *   must be a NeRF handle in TGTC_PREC_FP16_FP6 (any other precision -> TGTC_ERR_UNSUPPORTED: tgtc_geometry_trunk takes those);
+ *   trunk_bytes >= tgtc_geometry_trunk_bytes(TGTC_PREC_FP16X3, count).  One launch, no synchronisation, every byte of every tile
+ *   written (columns past the list's end hold the last live sample's fragments): two builds are byte-equal.
+ * Identity: hi and lo of list entry i are the split of relu(base_remap) as tgtc_nerf_forward on the same handle returns it for the
+ *   point o + t d of that entry, bit for bit: the same dense_mx sequence on the same operands.
+ * tgtc_geometry_trunk_read (the seam the tests look into a plane through; DEVICE buffers, one launch, no synchronisation): a
+ *   plane of `precision` (TGTC_PREC_FP16X3 or TGTC_PREC_FP16) of `count` list entries as floats, hi [count,256] and lo
+ *   [count,256]: base_remap of list entry i, feature f.  lo may be NULL and is not written for TGTC_PREC_FP16.  count == 0 ->
+ *   TGTC_OK, nothing launched.
+ * Errors (before a device is touched): as tgtc_geometry_trunk;  tgtc_geometry_trunk_read: count < 0, another precision, a null
+ *   plane or hi with count > 0, a plane below tgtc_geometry_trunk_bytes(precision, count) -> TGTC_ERR_ARG;  count >= 2^31 ->
+ *   TGTC_ERR_UNSUPPORTED. */
+int tgtc_geometry_trunk_mx(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse, int n_fine,
+                           const void* cache, size_t cache_bytes, int64_t count, void* trunk, size_t trunk_bytes, void* stream);
+int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t trunk_bytes, int64_t count, float* hi, float* lo,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

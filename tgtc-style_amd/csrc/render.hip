@@ -49,6 +49,9 @@ int styled_trunk_plane_impl(const tgtc_net* nerf, const double* rays_o, const do
 int styled_restyle_plane_impl(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
                               const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
                               int64_t count, const void* plane, float* rgb_live, hipStream_t st);
+int styled_trunk_plane_mx_impl(const tgtc_net* nerf, const double* rays_o, const double* rays_d, int64_t R, int N,
+                               const uint32_t* live, const float* ts_live, int64_t count, void* plane, hipStream_t st);
+int trunk_plane_read_impl(bool fp16, const void* plane, int64_t count, float* hi, float* lo, hipStream_t st);
 int launch_composite_live(const uint32_t* ray_start, const uint32_t* live, const float* w_live, const float* rgb_live, int64_t R,
                           int N, int K, int64_t count, float* rgb_exp, hipStream_t st);
 int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w_f, const float* t_fine, int64_t R, int N,
@@ -834,4 +837,45 @@ extern "C" int tgtc_restyle_rays_trunk_folded_mx(const tgtc_net* style, const do
                                                  void* stream) {
     return restyle_rays_trunk("restyle_rays_trunk_folded_mx", true, true, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
                               cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the plane from an fp16mx handle
+// tgtc_geometry_trunk's arguments and checks in its order; the handle is in TGTC_PREC_FP16_FP6 and the plane it writes is the
+// TGTC_PREC_FP16X3 plane (csrc/mlp_trunk_mx.hip)
+extern "C" int tgtc_geometry_trunk_mx(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
+                                      int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
+                                      size_t trunk_bytes, void* stream) {
+    TGTC_REQUIRE(R >= 0 && count >= 0, "geometry_trunk_mx: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk_mx: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt || R == 0, "geometry_trunk_mx: count %lld exceeds the %lld samples", (long long)count,
+                 (long long)(R * nt));
+    TGTC_REQUIRE(fine, "geometry_trunk_mx: null handle");
+    TGTC_REQUIRE(fine->kind == 0, "geometry_trunk_mx: fine must be a NeRF handle");
+    if (fine->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk_mx: built for fp16mx handles only (tgtc_geometry_trunk takes fp16x3 and fp16)");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && cache && (trunk || count == 0), "geometry_trunk_mx: null pointer");
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "geometry_trunk_mx: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    const size_t need = tgtc_geometry_trunk_bytes(TGTC_PREC_FP16X3, count);
+    TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk_mx: plane of %zu bytes, need %zu", trunk_bytes, need);
+    if (count == 0) return TGTC_OK;
+    return styled_trunk_plane_mx_impl(fine, rays_o, rays_d, R, nt, gc.live, gc.ts_live, count, trunk, as_stream(stream));
+}
+
+extern "C" int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t trunk_bytes, int64_t count, float* hi, float* lo,
+                                        void* stream) {
+    TGTC_REQUIRE(count >= 0, "geometry_trunk_read: bad argument");
+    TGTC_REQUIRE(precision == TGTC_PREC_FP16X3 || precision == TGTC_PREC_FP16,
+                 "geometry_trunk_read: a plane exists in fp16x3 and fp16 only (got precision %d)", precision);
+    if (count >= ((int64_t)1 << 31)) return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk_read: count >= 2^31");
+    if (count == 0) return TGTC_OK;
+    TGTC_REQUIRE(trunk && hi, "geometry_trunk_read: null pointer");
+    const size_t need = tgtc_geometry_trunk_bytes(precision, count);
+    TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk_read: plane of %zu bytes, need %zu", trunk_bytes, need);
+    return trunk_plane_read_impl(precision == TGTC_PREC_FP16, trunk, count, hi, lo, as_stream(stream));
 }

@@ -125,6 +125,9 @@ _OPTIONAL = {
     "tgtc_style_mx_read": [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t],
     "tgtc_restyle_rays_trunk_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
                                           c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_geometry_trunk_mx": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p,
+                               c_size_t, c_void_p],
+    "tgtc_geometry_trunk_read": [c_int, c_void_p, c_size_t, c_int64, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -24,7 +24,9 @@ class GeometryCache:
     `trunk` (None unless asked for: RayRenderer.build_trunk) is the trunk plane of tgtc_geometry_trunk, a uint8 device tensor
     of trunk_nbytes(trunk_precision, count) bytes -- base_remap of every list entry as the style kernels' operand fragments,
     1 KiB per live sample in fp16x3, 512 B in fp16 -- from which `restyle` runs without any NeRF network.  It is valid only
-    for this list and for style pairs packed in `trunk_precision` (a name of hip.PRECISIONS)."""
+    for this list and for style pairs packed in `trunk_precision` (a name of hip.PRECISIONS): the plane's LAYOUT.
+    `trunk_source` is the precision of the NeRF handle that produced it (None without a plane): `trunk_precision`, or "fp16mx"
+    for the fp16x3 plane of tgtc_geometry_trunk_mx."""
     MAGIC, VERSION = 0x43475447, 1
     TRUNK_TILE_BYTES = 131072
 
@@ -32,7 +34,7 @@ class GeometryCache:
         self.buffer, self.R, self.N, self.count = buffer, int(R), int(N), int(count)
         self.min_weight, self.key = float(min_weight), key
         self.n_coarse, self.n_fine = n_coarse, n_fine
-        self.trunk = self.trunk_precision = None
+        self.trunk = self.trunk_precision = self.trunk_source = None
         if buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.numel() < self.nbytes(self.R, self.count):
             raise ValueError("GeometryCache: the buffer must be uint8 [>= %d] for R = %d, count = %d"
                              % (self.nbytes(self.R, self.count), self.R, self.count))
@@ -60,19 +62,25 @@ class GeometryCache:
             return 0
         return (count + per_tile - 1) // per_tile * cls.TRUNK_TILE_BYTES
 
-    def attach_trunk(self, trunk, precision):
-        """Take `trunk` as this cache's plane.  ValueError unless it is uint8 [trunk_nbytes(precision, count)]."""
+    def attach_trunk(self, trunk, precision, source=None):
+        """Take `trunk` as this cache's plane.  ValueError unless it is uint8 [trunk_nbytes(precision, count)].
+        source: the precision of the NeRF handle that produced it; None means `precision`, "fp16mx" goes with an fp16x3 plane
+        only (tgtc_geometry_trunk_mx), anything else is a ValueError."""
         if precision not in ("fp16x3", "fp16"):
             raise ValueError("GeometryCache: a trunk plane exists in fp16x3 and fp16 only (got %r)" % (precision,))
+        source = precision if source is None else source
+        if source != precision and (source, precision) != ("fp16mx", "fp16x3"):
+            raise ValueError("GeometryCache: a %s trunk plane comes from a %s NeRF handle, or an fp16x3 plane from an fp16mx one "
+                             "(got source %r)" % (precision, precision, source))
         need = self.trunk_nbytes(precision, self.count)
         if trunk.dtype != torch.uint8 or trunk.dim() != 1 or trunk.numel() != need:
             raise ValueError("GeometryCache: the %s trunk plane of %d list entries is uint8 [%d], got %s %s"
                              % (precision, self.count, need, trunk.dtype, list(trunk.shape)))
-        self.trunk, self.trunk_precision = trunk, precision
+        self.trunk, self.trunk_precision, self.trunk_source = trunk, precision, source
 
     def drop_trunk(self):
         """Release the plane; the cache restyles through the fine NeRF handle again."""
-        self.trunk = self.trunk_precision = None
+        self.trunk = self.trunk_precision = self.trunk_source = None
 
     def _view(self, name, dtype):
         off, words = self._planes(self.R, self.count)[0][name]
@@ -88,13 +96,16 @@ class GeometryCache:
     def save(self, path, with_trunk=False):
         """One file: the buffer (moved to the host) and the metadata.  The trunk plane is left out unless with_trunk (it is
         some 80 times the buffer, and build_trunk makes it again from a loaded cache in about one trunk pass); a file saved
-        without it is the file of a cache that never had one."""
+        without it is the file of a cache that never had one.  "trunk_source" is written where it differs from
+        "trunk_precision": a file without the key holds a plane from a handle of the plane's own precision."""
         d = {"buffer": self.buffer.detach().cpu(), "R": self.R, "N": self.N, "count": self.count,
              "min_weight": self.min_weight, "key": self.key, "n_coarse": self.n_coarse, "n_fine": self.n_fine}
         if with_trunk:
             if self.trunk is None:
                 raise ValueError("GeometryCache.save: with_trunk, but the cache carries no trunk plane")
             d["trunk"], d["trunk_precision"] = self.trunk.detach().cpu(), self.trunk_precision
+            if self.trunk_source != self.trunk_precision:
+                d["trunk_source"] = self.trunk_source
         torch.save(d, path)
 
     @classmethod
@@ -113,7 +124,7 @@ class GeometryCache:
                             and int(c.ray_start.min()) >= 0 and int(c.ray_start.max()) <= c.count):
             raise ValueError("GeometryCache.load: %s: the list leaves the sample range" % path)
         if d.get("trunk") is not None:
-            c.attach_trunk(d["trunk"].contiguous(), d.get("trunk_precision"))
+            c.attach_trunk(d["trunk"].contiguous(), d.get("trunk_precision"), d.get("trunk_source"))
             c.trunk = c.trunk.to(device)
         c.buffer = c.buffer.to(device)
         return c
@@ -318,11 +329,12 @@ class RayRenderer:
         return {"rgb": rgb, "t": t}
 
     def build_geometry(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, min_weight=0., key=None,
-                       keep_trunk=False):
+                       keep_trunk=False, trunk_precision=None):
         """Everything of `render_latents(..., min_weight=min_weight)` that depends on the rays alone -- coarse pass, fine
         depths, sigma pass, weights, compaction -- as a GeometryCache (about 12 bytes per live sample + 8 per ray).  The
         host reads the live count once here (one synchronisation per build); `restyle` has none.
-        keep_trunk: also `build_trunk` the cache (1 KiB per live sample in fp16x3, 512 B in fp16)."""
+        keep_trunk: also `build_trunk` the cache (1 KiB per live sample in fp16x3, 512 B in fp16); trunk_precision goes to
+        `build_trunk`."""
         hip.require_gpu(rays_o, rays_d)
         lib = hip.load()
         if n_fine <= 0:
@@ -349,13 +361,24 @@ class RayRenderer:
         hip.check(lib.tgtc_geometry_pack(hip.ptr(ws), R, n_coarse, n_fine, min_weight, count, hip.ptr(buf), buf.numel(),
                                          hip.stream()))
         cache = GeometryCache(buf, R, n_coarse + n_fine, count, min_weight, key, n_coarse, n_fine)
-        return self.build_trunk(cache, rays_o, rays_d) if keep_trunk else cache
+        return self.build_trunk(cache, rays_o, rays_d, trunk_precision=trunk_precision) if keep_trunk else cache
 
-    def build_trunk(self, cache, rays_o, rays_d):
+    def build_trunk(self, cache, rays_o, rays_d, trunk_precision=None):
         """Give `cache` its trunk plane: the fine NeRF trunk once over the cached list (tgtc_geometry_trunk; no coarse pass,
         no sigma pass, no synchronisation), base_remap kept as the style kernels' operand fragments in the fine handle's
         precision.  `restyle` then needs no NeRF network for this cache.  rays_o / rays_d must be the rays of the build.
-        Returns the cache."""
+        Returns the cache.
+        trunk_precision: None is that call.  "fp16x3" asks for an fp16x3 plane: from an fp16x3 fine handle the same call, from
+        an fp16mx fine handle tgtc_geometry_trunk_mx -- the trunk in fp16mx, base_remap split into the fp16x3 plane's hi / lo
+        fragments (`cache.trunk_source` is then "fp16mx"), which an fp16x3 style pair restyles from in fp16x3 or with
+        style_precision="fp16mx".  Every other combination is a ValueError before any launch.  No default selects it."""
+        from_mx = False
+        if trunk_precision is not None:
+            have = self.fine.packed().precision
+            if trunk_precision != "fp16x3" or have not in ("fp16x3", "fp16mx"):
+                raise ValueError("build_trunk: trunk_precision is None (the fine handle's own plane: fp16x3 or fp16) or 'fp16x3' "
+                                 "with a fine handle in fp16x3 or fp16mx (got %r, fine handle in %s)" % (trunk_precision, have))
+            from_mx = have == "fp16mx"
         hip.require_gpu(rays_o, rays_d, cache.buffer)
         lib = hip.load()
         if rays_o.shape[0] != cache.R:
@@ -363,11 +386,12 @@ class RayRenderer:
         rays_o = rays_o.to(torch.float64).contiguous()
         rays_d = rays_d.to(torch.float64).contiguous()
         fine = self.fine.packed()
-        plane = torch.empty(cache.trunk_nbytes(fine.precision, cache.count), dtype=torch.uint8, device=rays_o.device)
-        hip.check(lib.tgtc_geometry_trunk(fine.handle, hip.ptr(rays_o), hip.ptr(rays_d), cache.R, cache.n_coarse, cache.n_fine,
-                                          hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(plane), plane.numel(),
-                                          hip.stream()))
-        cache.attach_trunk(plane, fine.precision)
+        layout = "fp16x3" if from_mx else fine.precision
+        plane = torch.empty(cache.trunk_nbytes(layout, cache.count), dtype=torch.uint8, device=rays_o.device)
+        call = lib.tgtc_geometry_trunk_mx if from_mx else lib.tgtc_geometry_trunk
+        hip.check(call(fine.handle, hip.ptr(rays_o), hip.ptr(rays_d), cache.R, cache.n_coarse, cache.n_fine,
+                       hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(plane), plane.numel(), hip.stream()))
+        cache.attach_trunk(plane, layout, fine.precision)
         return cache
 
     def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None, use_trunk=None, style_precision=None):
