@@ -80,7 +80,12 @@ int tgtc_net_destroy(tgtc_net* net);
 int tgtc_net_precision(const tgtc_net* net);
 
 /* StyleNerf.forward (models.py:216-223): raw points / view dirs [M,3] double -> outputs.  Any output may be NULL.
- * base_remap float [M,256]; pts_enc float [M,63]; dirs_enc float [M,27]. */
+ * base_remap float [M,256]; pts_enc float [M,63]; dirs_enc float [M,27].
+ * Coordinate range (every entry point that encodes positions itself: this one, tgtc_nerf_forward_rays / _list, the render
+ * and restyle calls): the in-kernel encoder reduces 2^band x / (2 pi) in float64 and takes the quadrant from a 32-bit integer,
+ * so its accuracy does not depend on |x| up to |x| < 2^31 x 2 pi / (4 x 2^9) ~ 6.5e6 for positions (band 9) and
+ * 2^31 x 2 pi / (4 x 2^3) ~ 4.2e8 for directions (band 3); beyond that the quadrant saturates and sin / cos are wrong.  A sample with non-finite coordinates
+ * changes no other sample's outputs. */
 int tgtc_nerf_forward(const tgtc_net* net, const double* pts, const double* dirs, int64_t M,
                       float* rgb, float* sigma, float* base_remap, float* pts_enc, float* dirs_enc, void* stream);
 
