@@ -529,6 +529,49 @@ int tgtc_geometry_trunk_mx(const tgtc_net* fine, const double* rays_o, const dou
 int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t trunk_bytes, int64_t count, float* hi, float* lo,
                              void* stream);
 
+/* ------------------------------------------------------------------ the fp16x3+fp16mx pair in one call, without a plane
+ * Every stylised entry point above that takes a fine handle refuses a fine handle and a style handle of different precisions, and
+ * stays that way.  The three entry points here are the folded list entry points for the pair a TGTC_PREC_FP16_FP6 fine network
+ * forms with a TGTC_PREC_FP16X3 style handle that carries mx streams (tgtc_style_enable_mx): ONE persistent kernel
+ * (csrc/mlp_list_mx.hip) runs, per 128-entry tile of the list, the trunk of tgtc_geometry_trunk_mx and then the K latents of
+ * tgtc_restyle_rays_trunk_folded_mx, with base_remap parked in the workgroup's tile of slab region B of the style handle
+ * instead of a plane: nothing of 1 KiB per live sample is allocated, written to HBM for later or kept.  It is a mode the caller
+ * asks for; nothing selects it.
+ *
+ * tgtc_styled_forward_list_folded_mx: the arguments and rules of tgtc_styled_forward_list_folded -- rgb float [K,R,N,3] is
+ *   written at the samples live[0 .. *n_live) only (the caller zero-fills it), the list's length is read on the device, a
+ *   length of 0 writes nothing.  The kernel alone: the seam the tests use.
+ * tgtc_render_rays_styled_sparse_folded_mx: the arguments, workspace (tgtc_render_styled_sparse_folded_workspace_bytes), order
+ *   of work and live_count of tgtc_render_rays_styled_sparse_folded: fold, the geometry half, the zero-fill, the kernel above,
+ *   K compositing launches.  No synchronisation; the host never learns the list's length.
+ * tgtc_restyle_rays_folded_mx: the arguments and workspace (tgtc_restyle_folded_workspace_bytes) of tgtc_restyle_rays_folded:
+ *   fold, the compact form of the kernel over the cached list, the compositing launch, the depth copy.  count == 0: neither the
+ *   fold nor the kernel is launched, rgb_fine is +0, t_fine is copied.
+ * Handles: `fine` / `nerf` must be a NeRF handle in TGTC_PREC_FP16_FP6, `style` a style handle in TGTC_PREC_FP16X3 with mx
+ *   streams (tgtc_style_has_mx) -> TGTC_ERR_UNSUPPORTED otherwise (an fp16 pair has no lo halves), checked where the siblings
+ *   compare the two precisions.  Every other error and the check order are the sibling's: K < 1, null pointers, wrong handle
+ *   kinds, min_weight < 0 or NaN, count > R x N, buffers below their size functions -> TGTC_ERR_ARG;  K x R x N >= 2^31 or
+ *   K x count >= 2^31 -> TGTC_ERR_UNSUPPORTED;  R == 0 -> TGTC_OK.  The size and range checks come before the handles are looked
+ *   at, and nothing touches a device before the checks pass.
+ * Identity: a live sample is the same column of the same dense_mx sequences on the same operands, and base_remap's half8
+ *   values make a round trip through memory either way (the slab here, the plane there).  So rgb_fine and t_fine of
+ *   tgtc_restyle_rays_folded_mx are the BITS of tgtc_geometry_trunk_mx + tgtc_restyle_rays_trunk_folded_mx on the same cache, and
+ *   those of tgtc_render_rays_styled_sparse_folded_mx the bits of tgtc_geometry_build + tgtc_geometry_pack + that pair.
+ *   Deterministic: K latents in one call are the bits of K calls.
+ * Scratch slab: BOTH slab regions of the STYLE HANDLE are used; launches on one style handle must not overlap. */
+int tgtc_styled_forward_list_folded_mx(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                       const float* ts, const void* folded, int K, int64_t R, int N, const uint32_t* live,
+                                       const uint32_t* n_live, float* rgb, void* stream);
+int tgtc_render_rays_styled_sparse_folded_mx(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                             const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                             int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                             float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                             float* t_fine, uint32_t* live_count, void* stream);
+int tgtc_restyle_rays_folded_mx(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
+                                int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,7 @@ EXTRA = {
     "cull_weight": (float, -1.0),      # stylised renders: style networks only where the compositing weight exceeds it (HELP below)
     "geometry_cache": (str, ""),       # --share_geometry: directory of cached ray geometry, reused across runs (HELP below)
     "fold_latents": (None, False),     # --share_geometry with --cull_weight or --geometry_cache: one latent per (style, frame) (HELP below)
+    "style_precision": (str, ""),      # --fold_latents with a fine network in fp16mx: "fp16mx" runs the style networks in fp16mx (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
 }
@@ -78,6 +79,14 @@ HELP = {
                     "images agree with the run without the flag to the precision's rounding (at most one 8-bit level), the "
                     "depth images bit for bit, and a --geometry_cache directory serves both.  All rays of a call must "
                     "belong to one frame",
+    "style_precision": "fp16mx: with --render_valid_style --share_geometry --fold_latents, either --cull_weight >= 0 or "
+                       "--geometry_cache, and a --precision whose fine half is fp16mx (refused otherwise): the stylised frame "
+                       "of such a pair, e.g. fp16x3+fp16mx, which has none without the flag.  The fine NeRF trunk and the "
+                       "style networks of a 128-sample tile run in fp16mx in one kernel (the style pair stays packed in "
+                       "fp16x3 and gets a second pair of streams); colours are within 1e-3 of float64 per sample.  With "
+                       "--geometry_cache the frames are restyled from the cached geometry in the same kernel: no trunk "
+                       "plane is built or saved, and the files and keys of the directory are those of the run without the "
+                       "flag.  Default empty: off",
 }
 
 

@@ -19,4 +19,14 @@ int styled_restyle_plane_mx_impl(const tgtc_net* style, const double* rays_o, co
                                  int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count, const void* plane,
                                  float* rgb_live, hipStream_t st);
 
+// The same without a plane, behind the trunk of an fp16mx NeRF handle in the same launch (mlp_list_mx.hip; the callers in
+// render.hip have checked sizes, kinds, precisions and the mx streams).  Scattered: rgb [K,R,N,3] zero-filled by the caller, the
+// list's length a device word.  Compact: rgb_live [K,count,3], count >= 1.  Both slab regions of the style handle are used.
+int styled_forward_list_folded_mx_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                       const float* ts, const void* folded, int K, int64_t R, int N, const uint32_t* live,
+                                       const uint32_t* n_live, float* rgb, hipStream_t st);
+int styled_restyle_live_folded_mx_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                       const void* folded, int K, int64_t R, int N, const uint32_t* live, const float* ts_live,
+                                       int64_t count, float* rgb_live, hipStream_t st);
+
 }  // namespace tgtc

@@ -54,35 +54,7 @@ struct StyleMxArgs {
     int K;
 };
 
-struct StylePairMxMap {
-    static constexpr int NFRAG = kStylePairMxTable.bytes / 1024;
-    static constexpr int NSEG = 2;
-    static constexpr int chunk0(int i) { return i == 0 ? 0 : i == 1 ? kStylePairMxStyleOff / kChunkBytes : (1 << 30); }
-};
-
-// An operand set that comes out of memory as fp16 hi / lo fragments (8 k-steps: two 128-deep blocks) as blocks KB0, KB0 + 1 of
-// y: what mx_store_act leaves behind the last row tile of a block.  The hi values are >= 0 (both sets are ReLU outputs).
-template <int KB0, int NKB>
-__device__ __forceinline__ void mx_from_frags(const half8 (&h)[8][1], const half8 (&l)[8][1], MxAct<NKB>& y) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        unsigned mxk = 0;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const u4 r = __builtin_bit_cast(u4, h[4 * kb + s][0]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) mxk = pk_max_u16(mxk, r[e]);
-            y.h[4 * (KB0 + kb) + s] = h[4 * kb + s][0];
-        }
-        const int byte_h = block_exp_byte(mxk);
-        y.h6[KB0 + kb] = cvt_fp6(h[4 * kb][0], h[4 * kb + 1][0], h[4 * kb + 2][0], h[4 * kb + 3][0],
-                                 __builtin_bit_cast(float, byte_h << 23));
-        y.l6[KB0 + kb] = cvt_fp6(l[4 * kb][0], l[4 * kb + 1][0], l[4 * kb + 2][0], l[4 * kb + 3][0],
-                                 __builtin_bit_cast(float, (byte_h - 12) << 23));
-        y.sc[KB0 + kb] = byte_h | ((byte_h - 12) << 8);
-    }
-}
-
+// (StylePairMxMap and mx_from_frags, shared with styled_list_mx_kernel of mlp_list_mx.hip, are in mlp_mx.h)
 __global__ void __launch_bounds__(CfgMx::NWAVES * 64, CfgMx::NWAVES / 4) restyle_trunk_mx_kernel(StyleMxArgs a) {
     using C = CfgMx;
     constexpr const MxTable& T = kStylePairMxTable;

@@ -879,3 +879,128 @@ extern "C" int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t
     TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk_read: plane of %zu bytes, need %zu", trunk_bytes, need);
     return trunk_plane_read_impl(precision == TGTC_PREC_FP16, trunk, count, hi, lo, as_stream(stream));
 }
+
+// ------------------------------------------------------------------------------------------------ the fp16x3+fp16mx pair, no plane
+// The folded list entry points for a fine handle in TGTC_PREC_FP16_FP6 and an fp16x3 style handle with mx streams
+// (csrc/mlp_list_mx.hip: trunk and latents of a tile in one persistent kernel, base_remap parked in slab region B of the style
+// handle).  Arguments, workspaces, check order and the order of work are the siblings' (tgtc_styled_forward_list_folded,
+// tgtc_render_rays_styled_sparse_folded, tgtc_restyle_rays_folded); only the rule for the handles' precisions differs.
+static int list_mx_handles(const char* who, const tgtc_net* fine, const tgtc_net* style) {
+    if (fine->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the NeRF handle must be in fp16mx (the siblings without _mx take fp16x3 and fp16)", who);
+    if (style->precision != TGTC_PREC_FP16X3)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle must be in fp16x3 (an fp16 pair has no lo halves)", who);
+    if (!(style->mx && style->mx->dev))
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_styled_forward_list_folded_mx(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o,
+                                                  const double* rays_d, const float* ts, const void* folded, int K, int64_t R,
+                                                  int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
+    TGTC_REQUIRE(K >= 1, "styled_forward_list_folded_mx: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(R >= 0 && N >= 1, "styled_forward_list_folded_mx: bad argument");
+    constexpr int64_t kLimit = (int64_t)1 << 31;
+    if (R >= kLimit || R * (int64_t)N >= kLimit || R * (int64_t)N * K >= kLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "styled_forward_list_folded_mx: K x R x N >= 2^31 in one launch (chunk the rays)");
+    TGTC_REQUIRE(nerf && style, "styled_forward_list_folded_mx: null handle");
+    TGTC_REQUIRE(nerf->kind == 0 && style->kind == 1,
+                 "styled_forward_list_folded_mx: nerf must be a NeRF handle, style a style handle");
+    if (const int rc = list_mx_handles("styled_forward_list_folded_mx", nerf, style)) return rc;
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && folded && live && n_live && rgb, "styled_forward_list_folded_mx: null pointer");
+    return styled_forward_list_folded_mx_impl(nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live, rgb, as_stream(stream));
+}
+
+extern "C" int tgtc_render_rays_styled_sparse_folded_mx(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                                        const double* rays_o, const double* rays_d, const float* z, int K,
+                                                        int64_t R, int n_coarse, int n_fine, float near_, float far_,
+                                                        const float* jitter, float min_weight, void* workspace,
+                                                        size_t workspace_bytes, float* rgb_fine, float* t_fine,
+                                                        uint32_t* live_count, void* stream) {
+    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse_folded_mx: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse_folded_mx: min_weight must be >= 0 and not NaN (got %g)",
+                 (double)min_weight);
+    TGTC_REQUIRE(R >= 0, "render_rays_styled_sparse_folded_mx: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse_folded_mx: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(coarse && fine && style, "render_rays_styled_sparse_folded_mx: null handle");
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "render_rays_styled_sparse_folded_mx: coarse and fine must be NeRF handles, style a style handle");
+    if (const int rc = list_mx_handles("render_rays_styled_sparse_folded_mx", fine, style)) return rc;
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse_folded_mx: null pointer");
+    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
+    const size_t need = sw.total + align256(tgtc_style_folded_bytes(K));
+    TGTC_REQUIRE(workspace_bytes >= need, "render_rays_styled_sparse_folded_mx: workspace of %zu bytes, need %zu", workspace_bytes,
+                 need);
+    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + sw.total);
+    const MultiWorkspace& ws = sw.m;
+    hipStream_t st = as_stream(stream);
+    // 0. the K bias tables
+    int rc = style_fold_latents_impl(style, z, K, folded, st);
+    if (rc) return rc;
+    // 1-4. everything that depends on the ray alone
+    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
+                      stream);
+    if (rc) return rc;
+    // 5. dead samples keep colour +0
+    TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
+    // 6. fp16mx trunk + the folded style pair's fp16mx streams over the list (the host never learns its length)
+    rc = styled_forward_list_folded_mx_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    if (rc) return rc;
+    // 7. compositing over the shared sigma / depths
+    for (int k = 0; k < K; ++k) {
+        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, nullptr,
+                              nullptr, st);
+        if (rc) return rc;
+    }
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_restyle_rays_folded_mx(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                           const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                                           size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes,
+                                           float* rgb_fine, float* t_fine, void* stream) {
+    TGTC_REQUIRE(K >= 1, "restyle_rays_folded_mx: need K >= 1 latents (got %d)", K);
+    TGTC_REQUIRE(R >= 0 && count >= 0, "restyle_rays_folded_mx: bad argument");
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (R * nt >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded_mx: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    TGTC_REQUIRE(count <= R * nt || R == 0, "restyle_rays_folded_mx: count %lld exceeds the %lld samples", (long long)count,
+                 (long long)(R * nt));
+    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded_mx: K x count >= 2^31 (fewer latents per call)");
+    TGTC_REQUIRE(fine && style, "restyle_rays_folded_mx: null handle");
+    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays_folded_mx: fine must be a NeRF handle, style a style handle");
+    if (const int rc = list_mx_handles("restyle_rays_folded_mx", fine, style)) return rc;
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays_folded_mx: null pointer");
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays_folded_mx: cache of %zu bytes, need %zu", cache_bytes, gc.total);
+    const size_t need = tgtc_restyle_folded_workspace_bytes(count, K);
+    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays_folded_mx: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    float* rgb_live = static_cast<float*>(workspace);
+    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
+    int rc;
+    // 1. the K bias tables, then fp16mx trunk + the folded style pair's fp16mx streams over the cached list (nothing to launch
+    //    for an empty list)
+    if (count > 0) {
+        rc = style_fold_latents_impl(style, z, K, folded, st);
+        if (rc) return rc;
+        rc = styled_restyle_live_folded_mx_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        if (rc) return rc;
+    }
+    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
+    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
+    if (rc) return rc;
+    // 3. the depth image
+    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return TGTC_OK;
+}

@@ -128,6 +128,13 @@ _OPTIONAL = {
     "tgtc_geometry_trunk_mx": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p,
                                c_size_t, c_void_p],
     "tgtc_geometry_trunk_read": [c_int, c_void_p, c_size_t, c_int64, c_void_p, c_void_p, c_void_p],
+    "tgtc_styled_forward_list_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_render_rays_styled_sparse_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                                 c_int, c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_restyle_rays_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
+                                    c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -260,7 +260,8 @@ class RayRenderer:
         hip.check(rc)
         return ts
 
-    def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None, min_weight=None):
+    def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None, min_weight=None,
+                       style_precision=None):
         """The same rays under K latent sets in one call: zs float [K,R,32] -> dict rgb [K,R,3], t [R].
 
         The coarse pass, the fine depths and the fine NeRF trunk run once and are shared by the K images (one launch of
@@ -278,7 +279,25 @@ class RayRenderer:
         tgtc_render_rays_styled_sparse_folded: the latent columns of the style networks become K bias tables and the kernels
         run without the latent k-steps; no [K,R,32] plane exists.  Results differ from the [K,R,32] call with the rows
         repeated within the precision's error (zs = 0: bit for bit).  The dense multi-latent kernel has no such form: a
-        2-D zs with min_weight=None is a ValueError."""
+        2-D zs with min_weight=None is a ValueError.
+
+        style_precision: None is the calls above.  "fp16mx" is the culled frame of the fp16x3+fp16mx pair in one call
+        (tgtc_render_rays_styled_sparse_folded_mx): the geometry half as above, then trunk (fp16mx, the fine handle's own stream)
+        and the K latents (the pair's fp16mx streams, packed at the first such call) of every tile of the list in one kernel.
+        It needs zs [K,32], a min_weight, a fine handle in fp16mx and an fp16x3 style pair: anything else is a ValueError
+        before any launch.  rgb, t are the bits of build_geometry(min_weight, keep_trunk=True, trunk_precision="fp16x3") +
+        restyle(style_precision="fp16mx"), without the plane.  No default selects it."""
+        if style_precision not in (None, "fp16mx"):
+            raise ValueError("render_latents: style_precision is None or 'fp16mx', got %r" % (style_precision,))
+        mx = style_precision == "fp16mx"
+        if mx:
+            if self.style is None or zs is None or zs.dim() != 2:
+                raise ValueError("render_latents: style_precision='fp16mx' takes a style pair and frame-constant latents zs [K,32]")
+            if min_weight is None:
+                raise ValueError("render_latents: style_precision='fp16mx' needs a min_weight (the culled render)")
+            if self.fine.packed().precision != "fp16mx" or self.style.packed().precision != "fp16x3":
+                raise ValueError("render_latents: style_precision='fp16mx' needs a fine handle in fp16mx and an fp16x3 style pair "
+                                 "(fine %s, pair %s)" % (self.fine.packed().precision, self.style.packed().precision))
         if zs is not None and zs.dim() == 2 and min_weight is None:
             raise ValueError("zs [K,32] (latents constant over the rays) needs a min_weight: the dense multi-latent kernel has "
                              "no folded form")
@@ -318,6 +337,9 @@ class RayRenderer:
         if min_weight is not None:
             live = torch.zeros((), device=dev, dtype=torch.int32)
             call = lib.tgtc_render_rays_styled_sparse_folded if folded else lib.tgtc_render_rays_styled_sparse
+            if mx:
+                self.style.packed().enable_mx()                     # a no-op from the second call on
+                call = lib.tgtc_render_rays_styled_sparse_folded_mx
             hip.check(call(self.coarse.packed().handle, self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o),
                            hip.ptr(rays_d), hip.ptr(zs), K, R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
                            min_weight, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(live), hip.stream()))
@@ -409,8 +431,11 @@ class RayRenderer:
         style_precision: None runs the style networks in the pair's own precision.  "fp16mx" runs them in fp16mx
         (tgtc_restyle_rays_trunk_folded_mx: one fp16 product and two block-scaled fp6 corrections instead of three fp16
         products; 1e-3 of float64 per sample instead of 5e-5) on a second pair of streams the fp16x3 pair packs at the first
-        such call.  That form exists for zs [K,32], a cache with an fp16x3 trunk plane and an fp16x3 style pair only: anything
-        else is a ValueError before any launch.  No default selects it."""
+        such call.  That form exists for zs [K,32] and an fp16x3 style pair only, from a cache with an fp16x3 trunk plane or --
+        when the cache carries no plane, or use_trunk=False -- behind THIS RENDERER'S FINE HANDLE IN fp16mx
+        (tgtc_restyle_rays_folded_mx: trunk and latents of a tile in one kernel, base_remap parked in the style handle's
+        slab; no plane is allocated and `cache.trunk` is left alone; the bits of the plane path on a plane of
+        build_trunk(trunk_precision="fp16x3")).  Anything else is a ValueError before any launch.  No default selects it."""
         if self.style is None:
             raise ValueError("restyle needs a style pair")
         if style_precision not in (None, "fp16mx"):
@@ -419,11 +444,15 @@ class RayRenderer:
         if mx:
             if zs.dim() != 2:
                 raise ValueError("restyle: style_precision='fp16mx' takes frame-constant latents zs [K,32], got %s" % list(zs.shape))
-            if use_trunk is False or cache.trunk is None:
-                raise ValueError("restyle: style_precision='fp16mx' restyles from a trunk plane (build_trunk)")
-            if cache.trunk_precision != "fp16x3" or self.style.packed().precision != "fp16x3":
-                raise ValueError("restyle: style_precision='fp16mx' needs an fp16x3 trunk plane and an fp16x3 style pair (plane %s, "
-                                 "pair %s)" % (cache.trunk_precision, self.style.packed().precision))
+            no_plane = use_trunk is False or cache.trunk is None
+            if no_plane and (self.fine is None or self.fine.packed().precision != "fp16mx"):
+                raise ValueError("restyle: style_precision='fp16mx' restyles from a trunk plane (build_trunk), or without one "
+                                 "behind a fine handle in fp16mx")
+            if no_plane and use_trunk:
+                raise ValueError("restyle: use_trunk=True, but the cache carries no trunk plane (build_trunk)")
+            if self.style.packed().precision != "fp16x3" or (not no_plane and cache.trunk_precision != "fp16x3"):
+                raise ValueError("restyle: style_precision='fp16mx' needs an fp16x3 style pair and, with a plane, an fp16x3 trunk "
+                                 "plane (plane %s, pair %s)" % (cache.trunk_precision, self.style.packed().precision))
         if use_trunk is None:
             use_trunk = cache.trunk is not None
         elif use_trunk and cache.trunk is None:
@@ -461,7 +490,8 @@ class RayRenderer:
         t = torch.empty(R, device=dev, dtype=torch.float32)
         if mx:
             self.style.packed().enable_mx()                         # a no-op from the second call on
-            call = lib.tgtc_restyle_rays_trunk_folded_mx
+            # with a plane the plane consumer; without one the list kernel behind the fp16mx fine handle (no plane is made)
+            call = lib.tgtc_restyle_rays_trunk_folded_mx if use_trunk else lib.tgtc_restyle_rays_folded_mx
         elif use_trunk:
             call = lib.tgtc_restyle_rays_trunk_folded if folded else lib.tgtc_restyle_rays_trunk
         if use_trunk:
@@ -469,7 +499,8 @@ class RayRenderer:
                            cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(cache.trunk),
                            cache.trunk.numel(), hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
             return {"rgb": rgb, "t": t, "live": cache.count}
-        call = lib.tgtc_restyle_rays_folded if folded else lib.tgtc_restyle_rays
+        if not mx:
+            call = lib.tgtc_restyle_rays_folded if folded else lib.tgtc_restyle_rays
         hip.check(call(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R,
                        cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(ws),
                        ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
@@ -680,7 +711,7 @@ def _cached_geometry(renderer, directory, name, key, build):
 
 
 def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None, geometry_cache=None,
-                         geometry_tag=None, fold_latents=False):
+                         geometry_tag=None, fold_latents=False, style_precision=None):
     """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
     `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
     style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
@@ -691,8 +722,13 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     loaded and the call becomes `RayRenderer.restyle`; otherwise the geometry is built, saved there and restyled.  The
     images are those of min_weight (None counts as 0) without the cache, bit for bit.
     fold_latents: the latent model is evaluated on ONE row per style and the calls take zs [K,32] (RayRenderer.render_latents /
-    restyle: the folded kernels); needs a min_weight or a geometry_cache, and every ray of a call in the same frame."""
+    restyle: the folded kernels); needs a min_weight or a geometry_cache, and every ray of a call in the same frame.
+    style_precision: None, or "fp16mx" for a renderer whose fine handle is in fp16mx (fold_latents only): handed to
+    RayRenderer.render_latents, or with a geometry_cache to RayRenderer.restyle on a cache without a plane.  The geometry key
+    does not change: it describes the NeRF half only."""
     ds = dataloader.dataset
+    if style_precision is not None and not fold_latents:
+        raise ValueError("style_precision needs fold_latents (the fp16mx style kernels take zs [K,32])")
     if renderer is None or not hasattr(ds, 'frame_batches'):
         raise ValueError("share_geometry needs renderer=RayRenderer(...) and a dataset with the frame_batches hook")
     if fold_latents and min_weight is None and geometry_cache is None:
@@ -703,6 +739,7 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     # rays per call: K x R x nt samples stay below 2^31 and the per-sample colour of a call below 2 GiB
     per_call = max(1, min(((1 << 31) - 1) // (styles * nt), (2 << 30) // (styles * nt * 12)))
     rgbs, ts, have = [], [], 0
+    mode = {} if style_precision is None else {"style_precision": style_precision}
     if geometry_cache is not None:
         os.makedirs(geometry_cache, exist_ok=True)
         min_weight = 0. if min_weight is None else float(min_weight)
@@ -734,10 +771,11 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
                 cache = _cached_geometry(renderer, geometry_cache, 'geometry_%05d_%09d_%09d.pt' % (fid, p0, p1), key,
                                          lambda: renderer.build_geometry(ro, rd, args.N_samples, args.N_samples_fine, near=ds.near,
                                                                          far=ds.far, jitter=jitter, min_weight=min_weight, key=key))
-                out = renderer.restyle(cache, ro, rd, zs, key=key, n_coarse=args.N_samples, n_fine=args.N_samples_fine)
+                out = renderer.restyle(cache, ro, rd, zs, key=key, n_coarse=args.N_samples, n_fine=args.N_samples_fine,
+                                       **mode)
             else:
                 out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine,
-                                              near=ds.near, far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight)
+                                              near=ds.near, far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight, **mode)
             rgbs.append(out["rgb"].detach()), ts.append(out["t"].detach())
         have += R
         if have == res:           # a frame (this rank's part of it) is complete
@@ -754,7 +792,8 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
 
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
                  device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
-                 share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None, fold_latents=False):
+                 share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None, fold_latents=False,
+                 style_precision=None):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
     Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
@@ -763,8 +802,11 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     weight exceeds it, see RayRenderer.render_latents; None runs them on every sample.
     geometry_cache (share_geometry only): a directory in which the ray-only half of every call is kept and reused, see
     _render_style_shared; geometry_tag: a string that goes into the cache keys (what the driver cannot see, e.g. the NeRF
-    checkpoint step); fold_latents (share_geometry only): one latent per (style, frame), see _render_style_shared."""
+    checkpoint step); fold_latents (share_geometry only): one latent per (style, frame), see _render_style_shared;
+    style_precision (share_geometry with fold_latents only): "fp16mx", see _render_style_shared."""
     _require_fine(args)
+    if style_precision is not None and not (share_geometry and fold_latents):
+        raise ValueError("style_precision needs share_geometry=True and fold_latents=True")
     if geometry_cache is not None and not share_geometry:
         raise ValueError("geometry_cache needs share_geometry=True (the cache belongs to the walk by frames)")
     if fold_latents and not share_geometry:
@@ -776,7 +818,8 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     ds.mode = 'valid_style'
     if share_geometry:
         return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight,
-                                    geometry_cache=geometry_cache, geometry_tag=geometry_tag, fold_latents=fold_latents)
+                                    geometry_cache=geometry_cache, geometry_tag=geometry_tag, fold_latents=fold_latents,
+                                    style_precision=style_precision)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0

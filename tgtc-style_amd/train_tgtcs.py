@@ -273,7 +273,8 @@ def train(args):
             dataset.mode = 'valid_style'
             rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, share_geometry=args.share_geometry,
                                    geometry_cache=args.geometry_cache or None, geometry_tag="nerf_step=%d" % nerf_step,
-                                   fold_latents=args.fold_latents, **common, **styled)
+                                   fold_latents=args.fold_latents, style_precision=args.style_precision or None, **common,
+                                   **styled)
             print('Done, saving to', out)
             return out
         if args.render_train_style:
@@ -312,6 +313,19 @@ def main(argv=None):
     if args.fold_latents and not (args.cull_weight >= 0 or args.geometry_cache):
         raise SystemExit("train_tgtcs: --fold_latents needs --cull_weight >= 0 or --geometry_cache (the folded kernels are "
                          "those of the culled render and of the restyle; the dense multi-latent kernel has no folded form)")
+    if args.style_precision:
+        if args.style_precision != "fp16mx":
+            raise SystemExit("train_tgtcs: --style_precision takes fp16mx (got %r)" % args.style_precision)
+        if not (args.render_valid_style and args.share_geometry and args.fold_latents):
+            raise SystemExit("train_tgtcs: --style_precision needs --render_valid_style --share_geometry --fold_latents (the "
+                             "fp16mx style kernels take one latent per style and frame)")
+        if not (args.cull_weight >= 0 or args.geometry_cache):
+            raise SystemExit("train_tgtcs: --style_precision needs --cull_weight >= 0 or --geometry_cache (the fp16mx style "
+                             "kernels are those of the culled render and of the restyle)")
+        if args.precision.partition('+')[2] != "fp16mx" and args.precision != "fp16mx":
+            raise SystemExit("train_tgtcs: --style_precision fp16mx needs a --precision whose fine half is fp16mx, e.g. "
+                             "fp16x3+fp16mx (got %s; the kernel runs the fine trunk and the style networks of a tile together)"
+                             % args.precision)
     if args.expname is None:
         raise SystemExit("train_tgtcs: --expname (or --config) is required")
     try:
