@@ -208,6 +208,33 @@ int tgtc_net_set_cull(tgtc_net* net, int mode);
 float tgtc_net_live_fraction(const tgtc_net* net);
 long long tgtc_net_culled_renders(const tgtc_net* net);
 
+/* The stash: the two-phase fine pass without the second trunk.  The list launch above runs layers 0-7 and the sigma head
+ * again on samples the density launch has just finished; only base_remap and the colour head are new work.  With a STASH
+ * attached to the fine handle the two-phase pass is instead: a density launch that also parks layer 7's output (58 dwords per
+ * lane, 928 bytes per sample, + 4 for the sample index) of every sample with sigma > 0 in the stash; the zero-fill; a
+ * heads-only launch (base_remap, colour head) over the parked samples; tgtc_nerf_forward_list over the samples that found
+ * no room (an empty list runs its prologue alone); the dense compositing kernel.  Same bits as without a stash.
+ * The stash is a caller-owned device buffer of 1024 regions, one per wave of the two launches; a wave parks its live
+ * samples in its own region and what does not fit goes to the overflow list, so ANY size is correct and a size for the
+ * scene's live share is fast.  tgtc_net_stash_bytes(R, nt, share): the size at which a wave's region holds `share` of the
+ * samples it sees in a render of R rays x nt samples (0 for R <= 0, nt <= 0 or a negative share).  RayRenderer sizes it for
+ * the share above which AUTO stops culling (0.14): about 4 GB for 400 x 400 rays at 128 + 64.
+ * tgtc_net_set_stash(net, ptr, bytes): attach (ptr aligned to 256 bytes; the buffer stays the caller's and must outlive
+ * every render that uses it) or, with (NULL, 0), detach.  TGTC_ERR_UNSUPPORTED for a handle that is not TGTC_PREC_FP16_FP6;
+ * TGTC_ERR_ARG for a misaligned pointer or fewer bytes than one slot per region (tgtc_net_stash_bytes(1, 1, 0)).
+ * Without a stash, with TGTC_CULL_OFF, or where AUTO decides for the dense pass, nothing changes.  Renders that share a
+ * handle share its stash: like a shared workspace, they must be ordered on one stream.
+ * The two launches as entries of their own (tests, tools): tgtc_nerf_stash_fill writes sigma [R,N] as
+ * tgtc_nerf_forward_rays(rgb = NULL) does, zeroes `scratch` (8192 bytes: word 0 becomes the overflow list's length, words
+ * 64.. the live count of each wave) and fills the stash and `overflow` (uint32 [R x N]); tgtc_nerf_stash_heads writes
+ * sigmoid(rgb) of the parked samples into rgb [R,N,3] and nothing else.  Both need a stash attached (TGTC_ERR_ARG). */
+size_t tgtc_net_stash_bytes(int64_t R, int nt, float share);
+int tgtc_net_set_stash(tgtc_net* net, void* ptr, size_t bytes);
+int tgtc_nerf_stash_fill(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         float* sigma, uint32_t* scratch, uint32_t* overflow, void* stream);
+int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N,
+                          uint32_t* scratch, float* rgb, void* stream);
+
 /* ------------------------------------------------------------------ a8: latent table
  * models.py:490-506 StyleLatents_variational.forward.  latents float [S,F,D] device, mu float [S,D] device,
  * style_ids / frame_ids int64 [R] device.  tile7: the llff `repeat((7,1))` wrap (models.py:496). */

@@ -1,6 +1,7 @@
 // Fused positional encoding + NeRF MLP (reference models.py:63-117 MLP_style inside :182-223 StyleNerf;
 // D=8, W=256, skip at 4, view-dependent colour head).  One launch evaluates rgb / sigma for M samples;
 // the [M,256] activations of the 11 dense layers never leave registers (mlp_core.h).
+#include <cmath>
 #include <cstdlib>
 
 #include "mlp_core.h"
@@ -307,6 +308,37 @@ int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const doub
     return nerf_mx_launch(IN_LIST, true, a, st);
 }
 
+// ---- the stashed two-phase fine pass (mlp_nerf_mx2_stash.hip).  scratch: kSparseScratchBytes laid out as the compaction's
+// (word 0 the overflow list's length, the counts from kStashCountWord on: launch_live_stat sums them as they are)
+constexpr int kStashCountWord = 64;
+static_assert((kStashCountWord + kNerfStashRegions) * sizeof(uint32_t) <= kSparseScratchBytes, "counts must fit the scratch");
+
+static NerfStashArgs stash_args(const tgtc_net* net, uint32_t* scratch, uint32_t* ovf) {
+    return NerfStashArgs{net->stash, net->stash_cap, net->stash_stride, scratch + kStashCountWord, scratch, ovf};
+}
+
+// densities of all samples; layer 7's output of the live ones into the handle's stash, the rest of them into the list ovf
+// (length scratch[0]); scratch is zeroed here
+int nerf_stash_fill_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         float* sigma, uint32_t* scratch, uint32_t* ovf, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.sigma = sigma;
+    a.bias = net->dev;
+    a.stream = net->dev + net->bias_bytes;
+    TGTC_HIP_CHECK(hipMemsetAsync(scratch, 0, kSparseScratchBytes, st));
+    return nerf_mx2_stash_launch(a, stash_args(net, scratch, ovf), st);
+}
+
+// rgb[s] of the samples the stash holds (scratch as nerf_stash_fill_impl left it)
+int nerf_stash_heads_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N, uint32_t* scratch,
+                          float* rgb, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.rgb = rgb;
+    a.bias = net->dev;
+    a.stream = net->dev + net->heads_off;
+    return nerf_mx2_heads_launch(a, stash_args(net, scratch, nullptr), st);
+}
+
 }  // namespace tgtc
 
 using namespace tgtc;
@@ -324,7 +356,7 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
             return fail(TGTC_ERR_UNSUPPORTED, "nerf_create: layer %d is %dx%d, kernels are built for %dx%d (D=8, W=256, PE 10/4, viewdirs)",
                         i, layers[i].out_features, layers[i].in_features, want[i][0], want[i][1]);
     }
-    std::vector<char> bias_region, stream;
+    std::vector<char> bias_region, stream, heads;
     int n_frags = 0;
     // per-feature scales of the ReLU trunk balanced by powers of two first (mlp_pack.h, EqualisedNet): the same function,
     // numbers that every precision mode represents well.  base_remap's rows stay: it is an output of the operator.
@@ -337,6 +369,7 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     if (precision == TGTC_PREC_FP16_FP6) {
         const int rc = nerf_mx_pack(layers, bias_region, stream);
         if (rc != TGTC_OK) return rc;
+        nerf_mx_heads_stream(stream, heads);
     } else {
         PackedNet p = pack_layers(nerf_specs(layers), precision == TGTC_PREC_FP16X3);
         if (p.n_frags != NerfLayout::kFragsFull || (int)p.bias.size() != NerfLayout::kBiasFloats)
@@ -367,7 +400,9 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     net->n_frags = n_frags;
     // + one ring of slack: the fused ray kernel rounds a pass up to a whole number of rings and fetches (never reads)
     // the chunks behind the stream's end (mlp_core.h, WeightStream PERSIST)
-    size_t total = net->bias_bytes + net->stream_bytes + kRingBytes;
+    // fp16mx: + the heads' own stream (REMAP / C0 / C1 again, whole rings: the stashed fine pass, mlp_nerf_mx2_stash.hip)
+    net->heads_off = net->bias_bytes + net->stream_bytes + kRingBytes;
+    size_t total = net->heads_off + heads.size();
     hipError_t e = hipMalloc((void**)&net->dev, total);
     if (e != hipSuccess) {
         (void)hipHostFree(const_cast<uint64_t*>(net->cull->landed));
@@ -378,6 +413,7 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
     std::vector<char> host(total, 0);
     std::memcpy(host.data(), bias_region.data(), bias_region.size());
     std::memcpy(host.data() + net->bias_bytes, stream.data(), net->stream_bytes);
+    if (!heads.empty()) std::memcpy(host.data() + net->heads_off, heads.data(), heads.size());
     e = hipMemcpy(net->dev, host.data(), total, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(net->dev);
@@ -413,6 +449,60 @@ extern "C" int tgtc_net_set_cull(tgtc_net* net, int mode) {
     TGTC_REQUIRE(mode == TGTC_CULL_AUTO || mode == TGTC_CULL_OFF || mode == TGTC_CULL_ON, "net_set_cull: bad mode %d", mode);
     net->cull->mode = mode;
     return TGTC_OK;
+}
+
+extern "C" size_t tgtc_net_stash_bytes(int64_t R, int nt, float share) {
+    if (R <= 0 || nt <= 0 || !(share >= 0.0f)) return 0;
+    // a wave of the producer sees 32 samples of every grid-th pass of 128: its region holds `share` of them
+    int cus = 0;
+    if (cu_count(cus) != TGTC_OK || cus > kNerfStashMaxGrid) cus = kNerfStashMaxGrid;
+    const int64_t n_pass = (R * (int64_t)nt + 127) / 128;
+    const int64_t grid = n_pass < cus ? n_pass : cus;
+    const int64_t per_wave = (n_pass + grid - 1) / grid * 32;
+    int64_t cap = (int64_t)std::ceil((double)(share > 1.0f ? 1.0f : share) * (double)per_wave);
+    if (cap < 1) cap = 1;
+    const size_t stride = (cap * kNerfStashSlotBytes + 15) & ~(size_t)15;
+    return stride * kNerfStashRegions;
+}
+
+extern "C" int tgtc_net_set_stash(tgtc_net* net, void* ptr, size_t bytes) {
+    TGTC_REQUIRE(net && net->kind == 0, "net_set_stash: not a NeRF handle");
+    if (!ptr && bytes == 0) {
+        net->stash = nullptr, net->stash_cap = 0, net->stash_stride = 0;
+        return TGTC_OK;
+    }
+    if (net->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "net_set_stash: built for fp16+fp6 handles only (got precision %d)", net->precision);
+    TGTC_REQUIRE(ptr && ((size_t)ptr & 255) == 0, "net_set_stash: the stash must be a device pointer aligned to 256 bytes");
+    const size_t stride = bytes / kNerfStashRegions & ~(size_t)15;
+    size_t cap = stride / kNerfStashSlotBytes;
+    TGTC_REQUIRE(cap >= 1, "net_set_stash: %zu bytes hold no slot in each of the %d regions (need %zu)", bytes, kNerfStashRegions,
+                 tgtc_net_stash_bytes(1, 1, 0.0f));
+    if (cap > 0x40000000u) cap = 0x40000000u;
+    net->stash = static_cast<char*>(ptr), net->stash_cap = (unsigned)cap, net->stash_stride = stride;
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_nerf_stash_fill(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                                    int N, float* sigma, uint32_t* scratch, uint32_t* overflow, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_stash_fill: bad argument");
+    TGTC_REQUIRE(net->stash, "nerf_stash_fill: no stash attached (tgtc_net_set_stash)");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && sigma && scratch && overflow, "nerf_stash_fill: null pointer");
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_stash_fill: R x N >= 2^31 (chunk the rays)");
+    return nerf_stash_fill_impl(net, rays_o, rays_d, ts, R, N, sigma, scratch, overflow, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N,
+                                     uint32_t* scratch, float* rgb, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_stash_heads: bad argument");
+    TGTC_REQUIRE(net->stash, "nerf_stash_heads: no stash attached (tgtc_net_set_stash)");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && scratch && rgb, "nerf_stash_heads: null pointer");
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_stash_heads: R x N >= 2^31 (chunk the rays)");
+    return nerf_stash_heads_impl(net, rays_o, rays_d, R, N, scratch, rgb, as_stream(stream));
 }
 
 extern "C" float tgtc_net_live_fraction(const tgtc_net* net) {

@@ -214,4 +214,10 @@ struct tgtc_net {
     size_t fold_stream_off, fold_stream2_off, fold_wz_off;
     tgtc_cull_state* cull;  // NeRF handles only (tgtc_nerf_create)
     tgtc_style_mx* mx;      // style pairs only (tgtc_style_create)
+    // fp16mx NeRF handles only: the REMAP / C0 / C1 stream behind the full stream's slack (mlp_nerf_mx2_stash.hip), and the
+    // caller-owned stash of the two-phase fine pass (tgtc_net_set_stash; nullptr: none attached)
+    size_t heads_off;
+    char* stash;
+    size_t stash_stride;    // bytes between the regions
+    unsigned stash_cap;     // slots per region
 };

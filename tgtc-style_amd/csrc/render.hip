@@ -33,6 +33,10 @@ int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scr
 int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st);
 int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                            const uint32_t* live, const uint32_t* n_live, float* rgb, hipStream_t st);
+int nerf_stash_fill_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         float* sigma, uint32_t* scratch, uint32_t* ovf, hipStream_t st);
+int nerf_stash_heads_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N, uint32_t* scratch,
+                          float* rgb, hipStream_t st);
 
 int styled_restyle_live_impl(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o, const double* rays_d,
                              const float* z, int K, int64_t R, int N, const uint32_t* live, const float* ts_live, int64_t count,
@@ -236,7 +240,21 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
     const bool cull = listable && dead_bytes >= (size_t)M * 4 + kSparseScratchBytes && cull_wanted(c);
     uint32_t* scratch = nullptr;
     int rc;
-    if (cull) {
+    if (cull && fine->stash) {
+        // the stashed form (mlp_nerf_mx2_stash.hip): the density launch parks layer 7's output of its live samples, the
+        // heads-only launch reads it back; live samples that found their wave's region full are the list of the list launch
+        // (which runs its prologue alone when there are none).  The per-wave counts are the statistic's parts.
+        uint32_t* const ovf = reinterpret_cast<uint32_t*>(dead);
+        scratch = reinterpret_cast<uint32_t*>(dead + (size_t)M * 4);
+        rc = nerf_stash_fill_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ws.sigma_f, scratch, ovf, st);
+        if (rc) return rc;
+        TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)M * 3 * sizeof(float), st));   // unlisted samples keep colour +0
+        rc = nerf_stash_heads_impl(fine, rays_o, rays_d, R, nt, scratch, ws.rgb_f, st);
+        if (rc) return rc;
+        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ovf, scratch, ws.rgb_f, st);
+        if (rc) return rc;
+        ++c->culled;
+    } else if (cull) {
         uint32_t* const live = reinterpret_cast<uint32_t*>(dead);
         scratch = reinterpret_cast<uint32_t*>(dead + (size_t)M * 4);
         rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);

@@ -56,6 +56,10 @@ _SIGNATURES = {
     "tgtc_net_set_cull": [c_void_p, c_int],
     "tgtc_net_live_fraction": [c_void_p],
     "tgtc_net_culled_renders": [c_void_p],
+    "tgtc_net_stash_bytes": [c_int64, c_int, c_float],
+    "tgtc_net_set_stash": [c_void_p, c_void_p, c_size_t],
+    "tgtc_nerf_stash_fill": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_nerf_stash_heads": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
     "tgtc_composite": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_train": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
@@ -71,7 +75,7 @@ _SIGNATURES = {
                              c_void_p, c_void_p],
     "tgtc_latents_backward": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p],
 }
-_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_float, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
+_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_float, "tgtc_net_stash_bytes": c_size_t, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
              "tgtc_render_styled_multi_workspace_bytes": c_size_t,
              "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
              "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t,
@@ -223,6 +227,7 @@ class Net:
     def __init__(self, handle, precision):
         self.handle = handle
         self.precision = precision
+        self.stash = None
 
     def set_cull(self, mode):
         """The policy of the two-phase fine pass for chain renders with this net as the fine network (CULL_*)."""
@@ -235,6 +240,16 @@ class Net:
     def culled_renders(self):
         """How many of those renders took the two-phase fine pass."""
         return int(load().tgtc_net_culled_renders(self.handle))
+
+    def set_stash(self, buf):
+        """Attach a uint8 device tensor as the stash of the two-phase fine pass (tgtc_net_set_stash); None detaches.  The
+        handle keeps the tensor alive."""
+        if buf is None:
+            check(load().tgtc_net_set_stash(self.handle, None, 0))
+        else:
+            require_gpu(buf)
+            check(load().tgtc_net_set_stash(self.handle, ptr(buf), buf.numel() * buf.element_size()))
+        self.stash = buf
 
     def has_mx(self):
         """Whether this style pair carries its fp16mx streams (tgtc_style_enable_mx)."""

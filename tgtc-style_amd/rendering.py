@@ -139,7 +139,7 @@ class RayRenderer:
 
     _CULL = {None: hip.CULL_AUTO, False: hip.CULL_OFF, True: hip.CULL_ON}
 
-    def __init__(self, coarse, fine, style=None, fused=True, cull=None):
+    def __init__(self, coarse, fine, style=None, fused=True, cull=None, stash=None):
         """fused=True: the library's fastest path (TGTC_PATH_AUTO) -- a single persistent ray kernel where one is built, except
         for coarse fp16x3 + fine fp16mx, whose fine pass runs faster on the two-tile per-sample kernel (the split path).
         fused="single" asks for the single ray kernel and nothing else (TGTC_PATH_RAY_KERNEL).  fused=False forces the chain
@@ -148,12 +148,20 @@ class RayRenderer:
         cull (plain render on the chain, fine fp16mx): None leaves the two-phase fine pass to the library (TGTC_CULL_AUTO:
         densities first and the colour head on the live samples only once the fine handle has seen a low enough live
         share), True / False force it on / off.  The mode lives on the FINE HANDLE and is set by every plain render of
-        this renderer; the images are the same bits either way (include/tgtc_hip.h)."""
+        this renderer; the images are the same bits either way (include/tgtc_hip.h).
+        stash (the same renders): None attaches the stash of the two-phase pass as STASH_DEFAULT says, True / False force it,
+        a uint8 device tensor is attached as it is (any size from one slot per region up is correct);
+        it is allocated at the first such render, STASH_SHARE x 932 bytes per fine sample (about 4 GB for 400 x 400 rays at
+        128 + 64), and never with cull=False.  The same bits again."""
+        if not (stash is None or stash is True or stash is False or isinstance(stash, torch.Tensor)):
+            raise ValueError("stash must be None, True, False or a uint8 device tensor")
         if fused not in (True, False, "single"):
             raise ValueError("fused must be True, False or 'single'")
         if cull not in self._CULL:
             raise ValueError("cull must be None, True or False")
         self.coarse, self.fine, self.style, self.fused, self.cull = coarse, fine, style, fused, cull
+        self.stash = stash
+        self._stash = None
         self._ws = None
         self._ws_multi = None
         self._ws_restyle = None
@@ -161,6 +169,34 @@ class RayRenderer:
     def apply_cull(self):
         """Put this renderer's `cull` on the fine handle (a host call; handles are repacked when weights change)."""
         self.fine.packed().set_cull(self._CULL[self.cull])
+
+    # The live share the lazily attached stash is sized for: the library's kCullLiveThreshold (csrc/render.hip).  AUTO never
+    # culls above it, so a frame AUTO culls overflows only where single waves see more live samples than the frame's share.
+    STASH_SHARE = 0.14
+    # Whether plain chain renders attach a stash by default (stash=None); DESIGN 3.1 holds the measurement behind it.
+    STASH_DEFAULT = True
+
+    def _apply_stash(self, R, nt, device):
+        """Attach (lazily allocated, kept while large enough) or detach the stash of the two-phase fine pass on the fine
+        handle: fine handles in fp16mx only, never with cull=False (include/tgtc_hip.h, tgtc_net_set_stash)."""
+        net = self.fine.packed()
+        want = self.STASH_DEFAULT if self.stash is None else self.stash
+        if want is False or self.cull is False or net.precision != "fp16mx":
+            if net.stash is not None:
+                net.set_stash(None)
+            return
+        if isinstance(want, torch.Tensor):            # the caller's own buffer, whatever it holds
+            if net.stash is not want:
+                net.set_stash(want)
+            return
+        need = hip.load().tgtc_net_stash_bytes(R, nt, self.STASH_SHARE)
+        if self._stash is None or self._stash.numel() < need or self._stash.device != device:
+            if net.stash is not None:
+                net.set_stash(None)
+            self._stash = None   # (freed before its successor is allocated)
+            self._stash = torch.empty(need, dtype=torch.uint8, device=device)
+        if net.stash is not self._stash:
+            net.set_stash(self._stash)
 
     _REQUEST = {True: hip.PATH_AUTO, "single": hip.PATH_RAY_KERNEL, False: hip.PATH_CHAIN}
 
@@ -229,6 +265,8 @@ class RayRenderer:
                    hip.stream())
         if plain:
             self.apply_cull()
+            if path == hip.PATH_CHAIN:
+                self._apply_stash(R, n_coarse + n_fine, dev)
             hip.check(lib.tgtc_render_rays_plain(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o),
                                                  hip.ptr(rays_d), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
                                                  *rest))

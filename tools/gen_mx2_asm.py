@@ -2,6 +2,9 @@
 """Generator of the fp16mx (TGTC_PREC_FP16_FP6) NeRF pass on TWO column tiles per wave, one wave per SIMD.
 
     tools/gen_mx2_asm.py > tgtc-style_amd/csrc/mx2_asm_nerf.inc          (per-sample kernel csrc/mlp_nerf_mx2.hip)
+    tools/gen_mx2_asm.py stash > tgtc-style_amd/csrc/mx2_stash_asm_nerf.inc    (stashed fine pass csrc/mlp_nerf_mx2_stash.hip:
+                                                                          the sigma pass that hands layer 7's output out, and
+                                                                          the heads-only pass that takes it in)
 
 Why.  At one column tile per wave the fp16mx loop is bound by LDS bandwidth (profiles/r4_kernel_variants.md section 1: eight
 waves read the same 7 KiB of weight fragments per six MFMAs, 67 % LDS array busy at 0.40 of the matrix pipe).  LDS bytes per
@@ -96,9 +99,11 @@ def nerf_full_layers():
 
 
 class Pass2:
-    def __init__(self, table, layers, nq, padc, cfg=None, nkeep=24):
+    def __init__(self, table, layers, nq, padc, cfg=None, nkeep=24, keep0=0, bias_start=0):
         self.t, self.layers, self.nq, self.padc = table, layers, nq, padc
         self.nkeep = nkeep           # encoding registers per tile handed over: 24 (point + direction) or 16 (sigma-only pass)
+        self.keep0 = keep0           # the first of them (heads-only pass: 16, the direction's eight alone)
+        self.bias_start = bias_start  # bias / row-exponent table entry of the first layer (heads-only pass: behind the sigma head's)
         self.cfg = cfg or {}         # timing experiments (results wrong by construction): abl_epi, abl_reads, abl_ring, abl_barrier, abl_dma, abl_cvt
         self.e = Emitter()
         self.unit_op, self.unit_chunk = {}, {}
@@ -310,7 +315,7 @@ class Pass2:
         self.group_kb = {}
         rows = []
         q = 0
-        bias0 = 0
+        bias0 = self.bias_start
         for li, L in enumerate(self.layers):
             L.bias0 = bias0
             bias0 += 16 * L.rt
@@ -377,7 +382,7 @@ class Pass2:
 
         # ---- prologue: the encodings to their AGPRs, enter the pass, biases of three row tiles, groups 0 and 1
         for ct in range(NCT):
-            for i in range(self.nkeep):
+            for i in range(self.keep0, self.nkeep):
                 e.emit("v_accvgpr_write_b32 %s, %s" % (A(AKEEP + 24 * ct + i), V(H + 24 * ct + i)))
         self.boundary(0)
         for r in range(3):
@@ -515,6 +520,82 @@ def emit_pass(name, table, layers, nq, units, out, cfg=None, full=True):
     out.append("")
 
 
+def emit_stash_pass(name, table, layers, nq, units, out, cfg, heads):
+    """The two streams of the stashed fine pass (csrc/mlp_nerf_mx2_stash.hip).
+
+    heads = False: the sigma pass, instruction for instruction, whose activation set 1 -- layer 7's output, what the heads
+    read: hreg(1, ct), a6(1, ct), sc(1, ct, 0..1), 58 registers per lane and tile -- is an OUTPUT of the asm statement instead
+    of a clobber.  heads = True: REMAP, C0 and C1 alone on a group table of their own, the same 58 registers its input, the
+    direction's fragments handed over where the full pass takes them (keep registers 16..23 of each tile)."""
+    nchunk = (units * 1024 + CHUNK - 1) // CHUNK
+    padc = (nchunk + SLOTS - 1) // SLOTS * SLOTS
+    bias_start = 16 * sum(L.rt for L in nerf_full_layers()[:9]) if heads else 0
+    gen = Pass2(table, layers, nq, padc, cfg, nkeep=24 if heads else 16, keep0=16 if heads else 0, bias_start=bias_start)
+    lines = gen.generate()
+    stats = {}
+    for ln in lines:
+        k = ln.split()[0]
+        stats[k] = stats.get(k, 0) + 1
+    out.append("// pass %s: %d groups, %d layers, %d chunks (padded %d); %d instructions; %s" % (
+        name, nq, len(layers), nchunk, padc, len(lines), ", ".join("%s %d" % kv for kv in sorted(stats.items(), key=lambda kv: -kv[1])[:14])))
+    if heads:
+        out.append("// REMAP, C0 and C1 of the full pass on their own group table: x[ct] = layer 7's output as the sigma-stash pass left it, dkeep[ct] = Dh, Dl;")
+        out.append("// rows 0..2 of the colour head's accumulator come back in v18..v23")
+        out.append("constexpr int kMx2HeadsPadChunks = %d, kMx2HeadsUnits = %d;" % (padc, units))
+    else:
+        out.append("// the sigma pass, whose activation set 1 comes back in x[ct]: h = v%d.. (fp16 hi), a = a%d.. (e2m3 h6 | l6), sc = v%d.. (block scales)" % (
+            hreg(1, 0), a6(1, 0), sc(1, 0, 0)))
+    out.append("template <class Reader>")
+    if heads:
+        out.append("__device__ __forceinline__ void mx2_asm_%s(const Reader& rd, int wave, lds_cptr bias_lane, lds_cptr rs_lane, half8 (&dkeep)[2][2], Mx2Stash (&x)[2], float (&rgb)[2][3]) {" % name)
+    else:
+        out.append("__device__ __forceinline__ void mx2_asm_%s(const Reader& rd, int wave, lds_cptr bias_lane, lds_cptr rs_lane, half8 (&keep)[2][4], float (&sigma)[2], Mx2Stash (&x)[2]) {" % name)
+    out.append("    const unsigned src_lo = __builtin_amdgcn_readfirstlane((unsigned)(size_t)rd.ring.src[0]), src_hi = __builtin_amdgcn_readfirstlane((unsigned)((size_t)rd.ring.src[0] >> 32));")
+    out.append("    const unsigned ldsw = __builtin_amdgcn_readfirstlane((unsigned)(size_t)TGTC_LPTR(rd.ring.lds_wave));")
+
+    def rg(file, base, n):
+        return "{%s[%d:%d]}" % (file, base, base + n - 1)
+    mod = "+" if heads else "=&"
+    pinned_v, pinned_a = set(), set()
+    outs = []
+    if heads:
+        outs += ['"=&{v%d}"(rgb[%d][%d])' % (OUT + 2 + 3 * ct + i, ct, i) for ct in range(NCT) for i in range(3)]
+        pinned_v |= set(range(OUT + 2, OUT + 8))
+        for ct in range(NCT):
+            for i in range(2):
+                outs.append('"+%s"(dkeep[%d][%d])' % (rg("v", H + 24 * ct + 16 + 4 * i, 4), ct, i))
+            pinned_v |= set(range(H + 24 * ct + 16, H + 24 * ct + 24))
+    else:
+        outs += ['"=&{v%d}"(sigma[%d])' % (OUT + ct, ct) for ct in range(NCT)]
+        pinned_v |= set(range(OUT, OUT + 2))
+        for ct in range(NCT):
+            for i in range(4):
+                outs.append('"+%s"(keep[%d][%d])' % (rg("v", H + 24 * ct + 4 * i, 4), ct, i))
+            pinned_v |= set(range(H + 24 * ct, H + 24 * ct + 16))
+    for ct in range(NCT):
+        for i in range(8):
+            outs.append('"%s%s"(x[%d].h[%d])' % (mod, rg("v", hreg(1, ct) + 4 * i, 4), ct, i))
+        for i in range(6):
+            outs.append('"%s%s"(x[%d].a[%d])' % (mod, rg("a", a6(1, ct) + 4 * i, 4), ct, i))
+        for kb in range(2):
+            outs.append('"%s{v%d}"(x[%d].sc[%d])' % (mod, sc(1, ct, kb), ct, kb))
+        pinned_v |= set(range(hreg(1, ct), hreg(1, ct) + 32)) | {sc(1, ct, 0), sc(1, ct, 1)}
+        pinned_a |= set(range(a6(1, ct), a6(1, ct) + 24))
+    out.append("    asm volatile(")
+    out.append(block_text(lines))
+    ins = ['[lane_lo] "v"(rd.ring.lane_lo)', '[lane_hi] "v"(rd.ring.lane_hi)', '[b8_lo] "v"(rd.b8_lo)', '[b8_hi] "v"(rd.b8_hi)',
+           '[bias_lane] "v"(bias_lane)', '[rs_lane] "v"(rs_lane)', '[voff] "v"(rd.ring.voff)',
+           '[src_lo] "s"(src_lo)', '[src_hi] "s"(src_hi)', '[ldsw] "s"(ldsw)', '[wave] "s"(wave)']
+    clob = ['"memory"', '"scc"', '"m0"', '"s96"', '"s97"']
+    clob += ['"v%d"' % v for v in range(OUT, LAST_VGPR + 1) if v not in pinned_v]
+    clob += ['"a%d"' % a for a in range(N_AGPR) if a not in pinned_a]
+    out.append("        : " + ", ".join(outs))
+    out.append("        : " + ", ".join(ins))
+    out.append("        : " + ", ".join(clob) + ");")
+    out.append("}")
+    out.append("")
+
+
 def set_chunk(chunk):
     """ring of 128 KiB in chunks of `chunk` bytes (16 KiB: 8 slots, 32 KiB: 4 slots, half the boundaries)"""
     global CHUNK, SLOTS, LOOK, GPC
@@ -527,12 +608,22 @@ def set_chunk(chunk):
 
 def main():
     cfg = {}
+    stash = "stash" in sys.argv[1:]
     for a in sys.argv[1:]:
+        if a == "stash":
+            continue
         k, v = a.split("=")
         cfg[k] = int(v)
     set_chunk(cfg.get("chunk", CHUNK))
     out = ["// GENERATED by tools/gen_mx2_asm.py %s-- do not edit; see that file for the design." % ("".join(x + " " for x in sys.argv[1:])), ""]
     t = Table(NERF_SHAPES)
+    if stash:                                    # the two streams of the stashed fine pass, a file of their own
+        nq_s = t.first[9]
+        emit_stash_pass("nerf_sigma_stash_pass", t, nerf_full_layers()[:9], nq_s, t.bytes_upto(nq_s) // 1024, out, cfg, heads=False)
+        th = Table(NERF_SHAPES[9:])
+        emit_stash_pass("nerf_heads_pass", th, nerf_full_layers()[9:], th.n, th.bytes_upto(th.n) // 1024, out, cfg, heads=True)
+        print("\n".join(out))
+        return
     nq = t.first[12]
     units = t.bytes_upto(nq) // 1024
     emit_pass("nerf_full_pass", t, nerf_full_layers(), nq, units, out, cfg)
