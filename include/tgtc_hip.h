@@ -131,6 +131,25 @@ int tgtc_composite_backward(const float* rgb, const float* sigma, const float* t
 int tgtc_sample_fine(const double* rays_o, const double* rays_d, const float* ts, const float* weights,
                      int64_t R, int N, int n_fine, double* pts_out, float* ts_out, void* stream);
 
+/* a6 (weights only) + a7 (depths only) of a ray in ONE kernel: what the chain renders run between their passes when no
+ * coarse image is asked.  sigma [R,N], ts [R,N] -> ts_out [R,N+n_fine], the bits of tgtc_composite(weights) followed by
+ * tgtc_sample_fine on the same planes; weights_out [R,N] (the bits of tgtc_composite's weights) or NULL, in which case the
+ * weights never reach memory.  The sorted merge is two binary searches per element where a ray's coarse depths and its new
+ * samples are each non-decreasing (checked per ray on the device), the stable counting sort of tgtc_sample_fine otherwise.
+ * 3 <= N <= 256, n_fine >= 1, N + n_fine <= 512, else TGTC_ERR_UNSUPPORTED; null sigma / ts / ts_out -> TGTC_ERR_ARG;
+ * R == 0 -> TGTC_OK.  TGTC_PER_RAY_PAIR=1 in the environment makes the render entry points keep the two-kernel pair.
+ * _traced: the same launch; took_sort uint32 [R] receives 1 for a ray that took the counting sort, 0 for a merged ray. */
+int tgtc_coarse_to_fine(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out,
+                        float* weights_out, void* stream);
+int tgtc_coarse_to_fine_traced(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out,
+                               float* weights_out, uint32_t* took_sort, void* stream);
+
+/* tgtc_composite that reads rgb[r,i] only where sigma[r,i] > 0 and leaves every other sample out of the colour sums: over
+ * ANY bits at those entries (NaN patterns included) the outputs are the bits of tgtc_composite over a plane that holds +0
+ * there.  What the two-phase fine pass composites with, instead of zero-filling its colour plane.  weights may be NULL. */
+int tgtc_composite_live_colours(const float* rgb, const float* sigma, const float* ts, int64_t R, int N,
+                                float* rgb_exp, float* t_exp, float* weights, void* stream);
+
 /* ------------------------------------------------------------------ render paths
  * Which kernels render a frame is the caller's explicit choice, resolved by ONE rule (tgtc_render_path), so that a ray's
  * result never depends on the size of a buffer or on R:

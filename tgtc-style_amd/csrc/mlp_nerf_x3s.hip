@@ -16,6 +16,9 @@ namespace tgtc {
 #include TGTC_X3S_INC
 
 using CfgX3s = MlpCfg<4, 2, true, 4>;
+#ifndef TGTC_FRONT_ABL   // development switch, as TGTC_MX2_ABL of mlp_nerf_mx2.hip: what the HIP code in front of a pass costs
+#define TGTC_FRONT_ABL 0
+#endif
 
 __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long n_pass) {
     using C = CfgX3s;
@@ -55,9 +58,19 @@ __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long 
             const int g = lane >> 4, n = lane & 15;
             double pos[2][3], dir[2][3];
             long long sidx[2];
-            nerf_load_samples<2, IN_RAYS>(a, s_wave, n, pos, dir, sidx);
             half8 pe_h[2][2], pe_l[2][2], de_h[1][2], de_l[1][2];
+#if TGTC_FRONT_ABL & 1   // timing experiment: no sample loads, no encoding (results wrong by construction)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) pe_h[0][c] = pe_h[1][c] = pe_l[0][c] = pe_l[1][c] = half8{(_Float16)(float)(g + n)};
+#elif TGTC_FRONT_ABL & 4   // timing experiment: the sample loads (and their wait) without the encoders' arithmetic
+            nerf_load_samples<2, IN_RAYS>(a, s_wave, n, pos, dir, sidx);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                pe_h[0][c] = pe_h[1][c] = pe_l[0][c] = pe_l[1][c] = half8{(_Float16)(float)(pos[c][0] + pos[c][1] + pos[c][2])};
+#else
+            nerf_load_samples<2, IN_RAYS>(a, s_wave, n, pos, dir, sidx);
             nerf_encode<2, true, false>(a, pos, dir, sidx, g, pe_h, pe_l, de_h, de_l);
+#endif
 #pragma unroll
             for (int c = 0; c < 2; ++c) keep[c][0] = pe_h[0][c], keep[c][1] = pe_h[1][c], keep[c][2] = pe_l[0][c], keep[c][3] = pe_l[1][c];
         }

@@ -122,34 +122,78 @@ __global__ void __launch_bounds__(256) posenc_kernel(const T* __restrict__ x, lo
 // contracts (or does not contract) it the same way in both.
 __device__ __forceinline__ float composite_accumulate(float acc, float w, float c) { return acc + w * c; }
 
+// The same transmittance chain with the factors that are exactly 1 left out.  A sample with alpha == 0 has
+// keep = 1.0f - 0 + 1e-10f = 1.0f, and run * 1.0 is run, bit for bit (whatever run is): only the samples with alpha != 0 (a
+// NaN included) take a step of the sequential float64 product, in sample order -- one ballot per owned slot, then a walk
+// over the set bits with the factor read by v_readlane.  trans[k] = the product in front of sample lane * C + k, rounded to
+// float32: every sample behind the one that just multiplied takes the new value, so a sample (live or not) ends with
+// the product over the live samples in front of it -- the value the full chain gives it.
 template <int C>
+__device__ __forceinline__ void transmittance_of_live(const float (&alpha)[C], const float (&keep)[C], int lane, float (&trans)[C]) {
+    unsigned long long live[C], any = 0;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        live[k] = __ballot(alpha[k] != 0.0f);
+        any |= live[k];
+        trans[k] = 1.0f;
+    }
+    double run = 1.0;
+    while (any) {   // wave-uniform
+        const int l = __builtin_ctzll(any);
+        any &= any - 1;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            if ((live[k] >> l) & 1ull) {   // wave-uniform
+                run = run * (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, keep[k]), l));
+                const float t = (float)run;
+                const int cur = l * C + k;
+#pragma unroll
+                for (int kk = 0; kk < C; ++kk)
+                    if (lane * C + kk > cur) trans[kk] = t;
+            }
+        }
+    }
+}
+
+// LIVE_COLOURS: the transmittance chain runs over the samples with alpha != 0 alone (transmittance_of_live), and
+// a sample whose raw sigma is not > 0 neither loads its colour nor enters the colour sums.  Its alpha is
+// 1 - exp(-0 * delta) = 0 and its weight alpha * T = +0, so over a plane that holds +0 there it would enter as
+// acc + 0 * 0, which leaves acc (never -0: it starts at +0) unchanged: the flagged instance over ANY bits at the dead
+// entries equals the plain one over a zero-filled plane.  The depth sum and the weights are the plain instance's.
+template <int C, bool LIVE_COLOURS = false>
 __device__ __forceinline__ void composite_wave(const float* __restrict__ rgb, const float* __restrict__ sigma,
                                                const float* __restrict__ ts, int N, float* rgb_exp, float* t_exp,
                                                float* weights, const float* __restrict__ noise = nullptr,
                                                int white_bkgd = 0) {
     const int lane = threadIdx.x & 63;
     float alpha[C], tv[C], keep[C];
+    bool live[C];
 #pragma unroll
     for (int k = 0; k < C; ++k) {
         const int i = lane * C + k;
-        alpha[k] = 0.0f, tv[k] = 0.0f, keep[k] = 1.0f;
+        alpha[k] = 0.0f, tv[k] = 0.0f, keep[k] = 1.0f, live[k] = false;
         if (i < N) {
             const float t0 = ts[i];
             const float delta = (i + 1 < N) ? ts[i + 1] - t0 : 1e10f;       // utils.py:367-369
             const float raw = noise ? sigma[i] + noise[i] : sigma[i];      // training-time regulariser, :371-376
             const float dens = fmaxf(fmaxf(raw, 0.0f), 0.0f);               // relu(relu(.)) :365,:376
+            live[k] = raw > 0.0f;
             alpha[k] = 1.0f - expf(-dens * delta);
             tv[k] = t0;
             keep[k] = 1.0f - alpha[k] + 1e-10f;                             // :378
         }
     }
-    double run = 1.0;
     float trans[C];
-    for (int l = 0; l < 64; ++l) {   // wave-uniform trip count; samples behind N carry keep = 1
+    if constexpr (LIVE_COLOURS) {
+        transmittance_of_live<C>(alpha, keep, lane, trans);
+    } else {
+        double run = 1.0;
+        for (int l = 0; l < 64; ++l) {   // wave-uniform trip count; samples behind N carry keep = 1
 #pragma unroll
-        for (int k = 0; k < C; ++k) {
-            if (lane == l) trans[k] = (float)run;
-            run = run * (double)__shfl(keep[k], l);
+            for (int k = 0; k < C; ++k) {
+                if (lane == l) trans[k] = (float)run;
+                run = run * (double)__shfl(keep[k], l);
+            }
         }
     }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -161,7 +205,7 @@ __device__ __forceinline__ void composite_wave(const float* __restrict__ rgb, co
             const float w = alpha[k] * trans[k];
             wsum = wsum + w;
             if (weights) weights[i] = w;
-            if (rgb) {  // wave-uniform: the sigma-only coarse pass of a fused render has no colours
+            if (rgb && (!LIVE_COLOURS || live[k])) {  // rgb wave-uniform: the sigma-only coarse pass of a fused render has no colours
                 acc[0] = composite_accumulate(acc[0], w, rgb[i * 3 + 0]);
                 acc[1] = composite_accumulate(acc[1], w, rgb[i * 3 + 1]);
                 acc[2] = composite_accumulate(acc[2], w, rgb[i * 3 + 2]);
@@ -274,7 +318,7 @@ __global__ void __launch_bounds__(256) composite_backward_kernel(const float* __
                                d_rgb ? d_rgb + r * N * 3 : nullptr, d_sigma ? d_sigma + r * N : nullptr);
 }
 
-template <int C>
+template <int C, bool LIVE_COLOURS = false>
 __global__ void __launch_bounds__(256) composite_kernel(const float* __restrict__ rgb, const float* __restrict__ sigma,
                                                         const float* __restrict__ ts, long long R, int N,
                                                         float* __restrict__ rgb_exp, float* __restrict__ t_exp,
@@ -282,7 +326,7 @@ __global__ void __launch_bounds__(256) composite_kernel(const float* __restrict_
                                                         int white_bkgd) {
     const long long r = (long long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     if (r >= R) return;  // wave-uniform
-    composite_wave<C>(rgb ? rgb + r * N * 3 : nullptr, sigma + r * N, ts + r * N, N,
+    composite_wave<C, LIVE_COLOURS>(rgb ? rgb + r * N * 3 : nullptr, sigma + r * N, ts + r * N, N,
                       rgb_exp ? rgb_exp + r * 3 : nullptr, t_exp ? t_exp + r : nullptr,
                       weights ? weights + r * N : nullptr, noise ? noise + r * N : nullptr, white_bkgd);
 }
@@ -478,6 +522,175 @@ __global__ void __launch_bounds__(64) sample_fine_kernel(const double* __restric
     }
 }
 
+// ------------------------------------------------------------------------------- coarse -> fine, one kernel
+// composite_kernel<C> (weights only) followed by sample_fine_kernel, for a render that wants no coarse image: one wavefront
+// per ray, kCtfWaves rays per workgroup, each wave on an LDS strip of its own and no workgroup barrier (wave_sync hands
+// over).  The weights never leave the strip unless `weights_out` is given.
+//   weights   composite_wave's: alpha, keep, the sequential float64 product rounded to float32 per sample, alpha * trans,
+//             the product stepping over the factors that are exactly 1 (transmittance_of_live).
+//   cdf       sample_fine_kernel's: the same strided float64 sum, the same blocked float64 scan with
+//             ceil((N-2)/64) entries per lane, the same binary search, clamps and `den < 1e-5f` rule.
+//   merge     the ray's coarse depths and its inverse-CDF samples are two runs.  Where both are non-decreasing (neighbour
+//             compares, one ballot; a NaN fails them), the stable order of cat(coarse, fine) -- what the counting sort
+//             gives -- puts coarse element i at i + #(fine < ts[i]) and fine element j at j + #(coarse <= v_j): two
+//             binary searches in the other run instead of N + NF compares per element.  Otherwise (unsorted depths from
+//             a caller, a one-ulp inversion between two bins) the ray takes the counting sort.  Both compare with the
+//             float `<` / `==`, under which -0 and +0 tie.
+constexpr int kCtfWaves = 4;
+
+struct CtfStrip {
+    float all[kFineMaxTotal];   // coarse depths, then the new samples
+    float w[kFineMaxN];         // coarse weights, then the cdf
+};
+
+template <int C>
+__global__ void __launch_bounds__(64 * kCtfWaves) coarse_to_fine_kernel(const float* __restrict__ sigma_in,
+                                                                        const float* __restrict__ ts_in, long long R, int N,
+                                                                        int NF, float* __restrict__ ts_out,
+                                                                        float* __restrict__ weights_out,
+                                                                        unsigned* __restrict__ took_sort) {
+    __shared__ CtfStrip strips[kCtfWaves];
+    const long long r = (long long)blockIdx.x * kCtfWaves + (threadIdx.x >> 6);
+    if (r >= R) return;  // wave-uniform, and no workgroup barrier below
+    const int lane = threadIdx.x & 63;
+    float* const s_all = strips[threadIdx.x >> 6].all;
+    float* const s_w = strips[threadIdx.x >> 6].w;
+    const float* ts = ts_in + r * N;
+    const float* sigma = sigma_in + r * N;
+    const int B = N - 1;  // bins / cdf entries
+    const int P = N - 2;  // pdf entries
+    const int T = N + NF;
+
+    for (int i = lane; i < N; i += 64) s_all[i] = ts[i];
+    wave_sync();
+
+    // ---- weights (composite_wave<C>): lane l owns samples [l*C, l*C+C)
+    float alpha[C], keep[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const int i = lane * C + k;
+        alpha[k] = 0.0f, keep[k] = 1.0f;
+        if (i < N) {
+            const float t0 = s_all[i];
+            const float delta = (i + 1 < N) ? s_all[i + 1] - t0 : 1e10f;    // utils.py:367-369
+            const float dens = fmaxf(fmaxf(sigma[i], 0.0f), 0.0f);          // relu(relu(.)) :365,:376
+            alpha[k] = 1.0f - expf(-dens * delta);
+            keep[k] = 1.0f - alpha[k] + 1e-10f;                             // :378
+        }
+    }
+    float trans[C];
+    transmittance_of_live<C>(alpha, keep, lane, trans);
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const int i = lane * C + k;
+        if (i < N) {
+            const float w = alpha[k] * trans[k];
+            s_w[i] = w;
+            if (weights_out) weights_out[r * N + i] = w;
+        }
+    }
+    wave_sync();
+
+    // ---- cdf (sample_fine_kernel): sum of (w + 1e-5) over the interior weights (utils.py:575,584-585)
+    double part = 0.0;
+    for (int i = lane; i < P; i += 64) part += (double)(s_w[i + 1] + 1e-5f);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
+    const float total = (float)part;
+
+    // cdf[0] = 0, cdf[i+1] = float(sum_{j<=i} pdf[j]) with a float64 running sum (utils.py:586-587).  Blocked scan: lane
+    // owns pdf entries [lane*CP, lane*CP+CP), read into registers before any lane overwrites the weights with the cdf.
+    const int CP = (P + 63) / 64;   // <= 4
+    float pdf[4];
+    double lane_sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = lane * CP + k;
+        pdf[k] = 0.0f;
+        if (k < CP && i < P) {
+            pdf[k] = (s_w[i + 1] + 1e-5f) / total;
+            lane_sum += (double)pdf[k];
+        }
+    }
+    double incl = lane_sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double up = __shfl_up(incl, off);
+        if (lane >= off) incl += up;
+    }
+    double prefix = incl - lane_sum;
+    wave_sync();
+    if (lane == 0) s_w[0] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = lane * CP + k;
+        if (k < CP && i < P) {
+            prefix += (double)pdf[k];
+            s_w[i + 1] = (float)prefix;
+        }
+    }
+    wave_sync();
+
+    // ---- inverse CDF at u = linspace(0,1,NF) (utils.py:589-607); bins = midpoints of the coarse depths (utils.py:574)
+    for (int j = lane; j < NF; j += 64) {
+        const float u = linspace01(j, NF);
+        int lo = 0, hi = B;  // searchsorted(right=True): first index with cdf > u
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_w[mid] <= u) lo = mid + 1; else hi = mid;
+        }
+        const int below = max(lo - 1, 0), above = min(lo, B - 1);
+        const float c0 = s_w[below], c1 = s_w[above];
+        const float b0 = 0.5f * (s_all[below + 1] + s_all[below]), b1 = 0.5f * (s_all[above + 1] + s_all[above]);
+        float den = c1 - c0;
+        if (den < 1e-5f) den = 1.0f;
+        const float t = (u - c0) / den;
+        s_all[N + j] = b0 + t * (b1 - b0);
+    }
+    wave_sync();
+
+    // ---- are both runs non-decreasing?  Element e is compared with its successor inside its own run.
+    bool bad = false;
+    for (int e = lane; e < T - 1; e += 64)
+        if (e != N - 1) bad = bad || !(s_all[e] <= s_all[e + 1]);
+    const bool merge = __ballot(bad) == 0ull;   // wave-uniform
+    if (took_sort && lane == 0) took_sort[r] = merge ? 0u : 1u;
+
+    float* out = ts_out + r * T;
+    if (merge) {
+        for (int e = lane; e < T; e += 64) {
+            const float v = s_all[e];
+            int lo, hi;
+            if (e < N) {   // #(fine < v): first fine index whose value is not below v
+                lo = N, hi = T;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s_all[mid] < v) lo = mid + 1; else hi = mid;
+                }
+                out[e + (lo - N)] = v;
+            } else {       // #(coarse <= v): first coarse index whose value is above v
+                lo = 0, hi = N;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s_all[mid] <= v) lo = mid + 1; else hi = mid;
+                }
+                out[(e - N) + lo] = v;
+            }
+        }
+    } else {
+        // stable rank sort of the N+NF depths (utils.py:577), exact for any input order
+        for (int e = lane; e < T; e += 64) {
+            const float v = s_all[e];
+            int rank = 0;
+            for (int q = 0; q < T; ++q) {
+                const float x = s_all[q];
+                rank += (x < v) || (x == v && q < e);
+            }
+            out[rank] = v;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ latents
 // reference models.py:490-506
 __global__ void __launch_bounds__(256) latents_kernel(const float* __restrict__ latents, const float* __restrict__ mu,
@@ -645,7 +858,70 @@ int launch_sample_fine(const double* rays_o, const double* rays_d, const float* 
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;
 }
+
+// launch_composite (weights only) + launch_sample_fine (depths only) in one kernel; took_sort [R] or null: 1 where the ray
+// took the counting sort.
+int launch_coarse_to_fine(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out, float* weights_out,
+                          uint32_t* took_sort, hipStream_t st) {
+    if (N < 3 || N > kFineMaxN || n_fine < 1 || N + n_fine > kFineMaxTotal)
+        return fail(TGTC_ERR_UNSUPPORTED, "coarse_to_fine: N=%d n_fine=%d outside [3,%d] / total<=%d", N, n_fine, kFineMaxN,
+                    kFineMaxTotal);
+    const unsigned nb = blocks_for(R, kCtfWaves);
+#define TGTC_CTF(CC) coarse_to_fine_kernel<CC><<<nb, 64 * kCtfWaves, 0, st>>>(sigma, ts, R, N, n_fine, ts_out, weights_out, took_sort)
+    switch ((N + 63) / 64) {   // composite_kernel's C; N <= 256
+        case 1: TGTC_CTF(1); break;
+        case 2: TGTC_CTF(2); break;
+        case 3: TGTC_CTF(3); break;
+        default: TGTC_CTF(4); break;
+    }
+#undef TGTC_CTF
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+// launch_composite with colours read at live samples only (composite_wave's LIVE_COLOURS)
+int launch_composite_live_colours(const float* rgb, const float* sigma, const float* ts, int64_t R, int N, float* rgb_exp,
+                                  float* t_exp, float* weights, hipStream_t st) {
+    const unsigned nb = blocks_for(R, 4);
+    const int C = (N + 63) / 64;
+#define TGTC_COMPOSITE_LC(CC) composite_kernel<CC, true><<<nb, 256, 0, st>>>(rgb, sigma, ts, R, N, rgb_exp, t_exp, weights, nullptr, 0)
+    switch (C) {
+        case 1: TGTC_COMPOSITE_LC(1); break;
+        case 2: TGTC_COMPOSITE_LC(2); break;
+        case 3: TGTC_COMPOSITE_LC(3); break;
+        case 4: TGTC_COMPOSITE_LC(4); break;
+        case 5: case 6: case 7: case 8: TGTC_COMPOSITE_LC(8); break;
+        default: return fail(TGTC_ERR_UNSUPPORTED, "composite: N=%d samples per ray exceeds 512", N);
+    }
+#undef TGTC_COMPOSITE_LC
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
 }  // namespace tgtc
+
+extern "C" int tgtc_coarse_to_fine(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out,
+                                   float* weights_out, void* stream) {
+    TGTC_REQUIRE(R >= 0, "coarse_to_fine: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(sigma && ts && ts_out, "coarse_to_fine: null pointer");
+    return launch_coarse_to_fine(sigma, ts, R, N, n_fine, ts_out, weights_out, nullptr, as_stream(stream));
+}
+
+extern "C" int tgtc_coarse_to_fine_traced(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out,
+                                          float* weights_out, uint32_t* took_sort, void* stream) {
+    TGTC_REQUIRE(R >= 0, "coarse_to_fine_traced: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(sigma && ts && ts_out && took_sort, "coarse_to_fine_traced: null pointer");
+    return launch_coarse_to_fine(sigma, ts, R, N, n_fine, ts_out, weights_out, took_sort, as_stream(stream));
+}
+
+extern "C" int tgtc_composite_live_colours(const float* rgb, const float* sigma, const float* ts, int64_t R, int N,
+                                           float* rgb_exp, float* t_exp, float* weights, void* stream) {
+    TGTC_REQUIRE(R >= 0 && N >= 1, "composite_live_colours: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rgb && sigma && ts && rgb_exp && t_exp, "composite_live_colours: null pointer");
+    return launch_composite_live_colours(rgb, sigma, ts, R, N, rgb_exp, t_exp, weights, as_stream(stream));
+}
 
 extern "C" int tgtc_composite(const float* rgb, const float* sigma, const float* ts, int64_t R, int N,
                               float* rgb_exp, float* t_exp, float* weights, void* stream) {

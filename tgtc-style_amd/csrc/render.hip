@@ -2,6 +2,8 @@
 // that enqueues the kernels back to back on one stream (no host sync, no allocation).
 //   plain : rendering.py:27-51   (cal_geometry)
 //   styled: rendering.py:118-178 (render_style)   -- see mlp_style.hip
+#include <cstdlib>
+
 #include "common.h"
 
 #include "mlp_pack.h"
@@ -13,6 +15,10 @@ int launch_composite(const float* rgb, const float* sigma, const float* ts, int6
                      float* t_exp, float* weights, hipStream_t st);
 int launch_sample_fine(const double* rays_o, const double* rays_d, const float* ts, const float* weights, int64_t R,
                        int N, int n_fine, double* pts_out, float* ts_out, hipStream_t st);
+int launch_coarse_to_fine(const float* sigma, const float* ts, int64_t R, int N, int n_fine, float* ts_out, float* weights_out,
+                          uint32_t* took_sort, hipStream_t st);
+int launch_composite_live_colours(const float* rgb, const float* sigma, const float* ts, int64_t R, int N, float* rgb_exp,
+                                  float* t_exp, float* weights, hipStream_t st);
 int nerf_forward_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
                            int N, float* rgb, float* sigma, hipStream_t st);
 
@@ -204,11 +210,28 @@ extern "C" int tgtc_render_depths(const tgtc_net* coarse, const double* rays_o, 
     return launch_fused_depths(coarse->precision, a, as_stream(stream));
 }
 
+// ---- the per-ray stage between the passes: coarse densities -> weights -> fine depths
+// A render that wants no coarse image needs the coarse weights for the inverse CDF alone: ONE kernel computes them, samples
+// and merges (raypath.hip, coarse_to_fine_kernel), and the plane w_c stays unwritten.  With a coarse image asked, or with
+// TGTC_PER_RAY_PAIR=1 in the environment (read at every render: the yardstick the one kernel is held against), the
+// compositor writes w_c and the sampler reads it back.  The depths are the same bits either way.
+static int coarse_to_fine(const float* rgb_c, const float* sigma_c, const float* ts_c, float* w_c, const double* rays_o,
+                          const double* rays_d, int64_t R, int n_coarse, int n_fine, float* rgb_coarse, float* t_coarse,
+                          float* ts_f, hipStream_t st) {
+    if (!rgb_coarse && !t_coarse) {
+        const char* e = std::getenv("TGTC_PER_RAY_PAIR");
+        if (!(e && e[0] == '1')) return launch_coarse_to_fine(sigma_c, ts_c, R, n_coarse, n_fine, ts_f, nullptr, nullptr, st);
+    }
+    const int rc = launch_composite(rgb_c, sigma_c, ts_c, R, n_coarse, rgb_coarse, t_coarse, w_c, st);
+    if (rc) return rc;
+    return launch_sample_fine(rays_o, rays_d, ts_c, w_c, R, n_coarse, n_fine, nullptr, ts_f, st);
+}
+
 // ---- the two-phase fine pass of the plain chain
 // A fine sample with sigma <= 0 has alpha = 1 - exp(-relu(sigma) delta) = 0 exactly, weight 0 x T = +0, and enters the pixel
 // as acc + 0 x c: for finite colours the image does not need its colour head.  With the live share L of the samples, f the
-// full fine launch and s the density-only one, "densities, compaction, colours of the listed samples into a zero-filled
-// plane" costs s + L f + ~0.5 ms against f, a gain while L < L* = 1 - s / f.
+// full fine launch and s the density-only one, "densities, compaction, colours of the listed samples, a compositor that
+// reads colours at live samples only" costs s + L f + ~0.5 ms against f, a gain while L < L* = 1 - s / f.
 // kCullLiveThreshold = L* less a margin, both measured on the MI355X (tools/time_plain_cull.py --step0,
 // profiles/plain_cull_timing.json): on the fine depths of a real 400 x 400 render at 128 + 64, f = 53.10 ms and
 // s = 43.75 ms, L* = 0.176.  The margin is the whole spread of the live
@@ -248,7 +271,6 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         scratch = reinterpret_cast<uint32_t*>(dead + (size_t)M * 4);
         rc = nerf_stash_fill_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ws.sigma_f, scratch, ovf, st);
         if (rc) return rc;
-        TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)M * 3 * sizeof(float), st));   // unlisted samples keep colour +0
         rc = nerf_stash_heads_impl(fine, rays_o, rays_d, R, nt, scratch, ws.rgb_f, st);
         if (rc) return rc;
         rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ovf, scratch, ws.rgb_f, st);
@@ -261,7 +283,6 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         if (rc) return rc;
         rc = launch_compact_live(ws.sigma_f, M, 0.0f, live, scratch, nullptr, st);
         if (rc) return rc;
-        TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)M * 3 * sizeof(float), st));   // unlisted samples keep colour +0
         rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, st);
         if (rc) return rc;
         ++c->culled;
@@ -276,7 +297,10 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         }
         if (c) ++c->dense;
     }
-    rc = launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st);
+    // culled: rgb_f holds colours at the listed samples (sigma > 0) and whatever the plane held before everywhere else; the
+    // compositor reads it at the samples with sigma > 0 alone -- the bits of the plain instance over a zero-filled plane
+    rc = cull ? launch_composite_live_colours(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st)
+              : launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st);
     if (rc) return rc;
     if (scratch) {
         // (live count, M) -> the handle's pinned word, asynchronously; the next render's AUTO reads whatever has landed
@@ -316,9 +340,7 @@ extern "C" int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fi
     float* rgb_c = rgb_coarse ? ws.rgb_c : nullptr;
     rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, rgb_c, ws.sigma_c, st);
     if (rc) return rc;
-    rc = launch_composite(rgb_c, ws.sigma_c, ws.ts_c, R, n_coarse, rgb_coarse, t_coarse, ws.w_c, st);
-    if (rc) return rc;
-    rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+    rc = coarse_to_fine(rgb_c, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, rgb_coarse, t_coarse, ws.ts_f, st);
     if (rc) return rc;
     // fine pass + fine image: dense, or densities first and the colour head on the live samples only (fine_pass above)
     return fine_pass(fine, rays_o, rays_d, R, n_coarse + n_fine, ws, rgb_fine, t_fine, st);
@@ -372,9 +394,7 @@ extern "C" int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* f
     else
         rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
     if (rc) return rc;
-    rc = launch_composite(rgb_c, ws.sigma_c, ws.ts_c, R, n_coarse, rgb_coarse, t_coarse, ws.w_c, st);
-    if (rc) return rc;
-    rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+    rc = coarse_to_fine(rgb_c, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, rgb_coarse, t_coarse, ws.ts_f, st);
     if (rc) return rc;
     rc = styled_forward_rays_impl(fine, style, rays_o, rays_d, ws.ts_f, z, R, n_coarse + n_fine, ws.rgb_f, ws.sigma_f, st);
     if (rc) return rc;
@@ -420,9 +440,7 @@ extern "C" int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_
         if (rc) return rc;
         rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
         if (rc) return rc;
-        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
-        if (rc) return rc;
-        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+        rc = coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
         if (rc) return rc;
     }
     rc = styled_forward_rays_multi_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, ws.rgb_f, ws.sigma_f, st);
@@ -460,9 +478,7 @@ static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const doub
         if (rc) return rc;
         rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
         if (rc) return rc;
-        rc = launch_composite(nullptr, ws.sigma_c, ws.ts_c, R, n_coarse, nullptr, nullptr, ws.w_c, st);
-        if (rc) return rc;
-        rc = launch_sample_fine(rays_o, rays_d, ws.ts_c, ws.w_c, R, n_coarse, n_fine, nullptr, ws.ts_f, st);
+        rc = coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
         if (rc) return rc;
     }
     // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:

@@ -65,6 +65,9 @@ _SIGNATURES = {
     "tgtc_composite_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p],
     "tgtc_sample_fine": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "tgtc_coarse_to_fine": [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "tgtc_coarse_to_fine_traced": [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_composite_live_colours": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_render_workspace_bytes": [c_int64, c_int, c_int],
     "tgtc_render_path": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "tgtc_render_depths": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
