@@ -70,25 +70,33 @@ int launch_geometry_pack(const uint32_t* live, const float* ts_f, const float* w
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Carves consecutive planes out of one buffer, each rounded up to 256 bytes: every layout below is a sequence of take()s,
+// and `off` after the last one is the layout's size.
+struct PlaneCarver {
+    char* base;
+    size_t off;
+    template <typename T>
+    T* take(size_t count) {
+        T* p = reinterpret_cast<T*>(base + off);
+        off += align256(count * sizeof(T));
+        return p;
+    }
+};
+
 struct RenderWorkspace {
     float *ts_c, *sigma_c, *rgb_c, *w_c, *ts_f, *sigma_f, *rgb_f;
     size_t total;
     RenderWorkspace(char* base, int64_t R, int nc, int nf) {
         const int nt = nc + nf;
-        size_t off = 0;
-        auto take = [&](size_t floats) {
-            float* p = reinterpret_cast<float*>(base + off);
-            off += align256(floats * sizeof(float));
-            return p;
-        };
-        ts_c = take((size_t)R * nc);
-        sigma_c = take((size_t)R * nc);
-        rgb_c = take((size_t)R * nc * 3);
-        w_c = take((size_t)R * nc);
-        ts_f = take((size_t)R * nt);
-        sigma_f = take((size_t)R * nt);
-        rgb_f = take((size_t)R * nt * 3);
-        total = off;
+        PlaneCarver c{base, 0};
+        ts_c = c.take<float>((size_t)R * nc);
+        sigma_c = c.take<float>((size_t)R * nc);
+        rgb_c = c.take<float>((size_t)R * nc * 3);
+        w_c = c.take<float>((size_t)R * nc);
+        ts_f = c.take<float>((size_t)R * nt);
+        sigma_f = c.take<float>((size_t)R * nt);
+        rgb_f = c.take<float>((size_t)R * nt * 3);
+        total = c.off;
     }
 };
 
@@ -98,19 +106,14 @@ struct MultiWorkspace {
     size_t total;
     MultiWorkspace(char* base, int64_t R, int nc, int nf, int K) {
         const int nt = nc + nf;
-        size_t off = 0;
-        auto take = [&](size_t floats) {
-            float* p = reinterpret_cast<float*>(base + off);
-            off += align256(floats * sizeof(float));
-            return p;
-        };
-        ts_c = take((size_t)R * nc);
-        sigma_c = take((size_t)R * nc);
-        w_c = take((size_t)R * nc);
-        ts_f = take((size_t)R * nt);
-        sigma_f = take((size_t)R * nt);
-        rgb_f = take((size_t)K * R * nt * 3);
-        total = off;
+        PlaneCarver c{base, 0};
+        ts_c = c.take<float>((size_t)R * nc);
+        sigma_c = c.take<float>((size_t)R * nc);
+        w_c = c.take<float>((size_t)R * nc);
+        ts_f = c.take<float>((size_t)R * nt);
+        sigma_f = c.take<float>((size_t)R * nt);
+        rgb_f = c.take<float>((size_t)K * R * nt * 3);
+        total = c.off;
     }
 };
 
@@ -122,13 +125,14 @@ struct SparseWorkspace {
     uint32_t *live, *scratch;
     size_t total;
     SparseWorkspace(char* base, int64_t R, int nc, int nf, int K) : m(base, R, nc, nf, K) {
-        const size_t plane = align256((size_t)R * (nc + nf) * sizeof(float));
-        w_f = reinterpret_cast<float*>(base + m.total);
-        live = reinterpret_cast<uint32_t*>(base + m.total + plane);
-        scratch = reinterpret_cast<uint32_t*>(base + m.total + 2 * plane);
-        total = m.total + 2 * plane + kSparseScratchBytes;
+        PlaneCarver c{base, m.total};
+        w_f = c.take<float>((size_t)R * (nc + nf));
+        live = c.take<uint32_t>((size_t)R * (nc + nf));
+        scratch = c.take<uint32_t>(kSparseScratchBytes / sizeof(uint32_t));
+        total = c.off;
     }
 };
+static_assert(kSparseScratchBytes % 256 == 0, "the scratch is the workspace's last plane and is not rounded up");
 
 // A geometry cache (tgtc_geometry_pack): a 256-byte header, then t_fine [R], ray_start [R+1], live / ts_live / w_live [count],
 // every plane rounded up to 256 bytes.
@@ -137,21 +141,60 @@ struct GeometryCacheLayout {
     float *t, *ts_live, *w_live;
     size_t total;
     GeometryCacheLayout(char* base, int64_t R, int64_t count) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            char* p = base + off;
-            off += align256(bytes);
-            return p;
-        };
-        header = reinterpret_cast<uint32_t*>(take(256));
-        t = reinterpret_cast<float*>(take((size_t)R * 4));
-        ray_start = reinterpret_cast<uint32_t*>(take(((size_t)R + 1) * 4));
-        live = reinterpret_cast<uint32_t*>(take((size_t)count * 4));
-        ts_live = reinterpret_cast<float*>(take((size_t)count * 4));
-        w_live = reinterpret_cast<float*>(take((size_t)count * 4));
-        total = off;
+        PlaneCarver c{base, 0};
+        header = c.take<uint32_t>(64);
+        t = c.take<float>((size_t)R);
+        ray_start = c.take<uint32_t>((size_t)R + 1);
+        live = c.take<uint32_t>((size_t)count);
+        ts_live = c.take<float>((size_t)count);
+        w_live = c.take<float>((size_t)count);
+        total = c.off;
     }
 };
+
+// ---- the guards the entry points share; `who` is the entry's name without tgtc_, in front of every message
+constexpr int64_t kIndexLimit = (int64_t)1 << 31;   // samples, colours and list entries are indexed by 32 bits
+
+enum : unsigned {
+    kFold = 1,    // frame-constant latents z [K,32], folded into K bias tables at the end of the workspace
+    kMx = 2,      // the fp16mx form of the entry (its own rule for the handles' precisions, its own launch)
+    kPlane = 4,   // a restyle from the trunk plane: no NeRF handle
+};
+
+// the reference dereferences None when N_samples_fine == 0; require it instead
+static int sample_counts(int n_coarse, int n_fine) {
+    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    return TGTC_OK;
+}
+
+static int samples_indexable(const char* who, int64_t R, int nt) {
+    if (R * nt >= kIndexLimit) return fail(TGTC_ERR_UNSUPPORTED, "%s: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)", who);
+    return TGTC_OK;
+}
+
+static int colours_indexable(const char* who, int K, int64_t R, int nt) {
+    if (R >= kIndexLimit || R * nt >= kIndexLimit || R * nt * K >= kIndexLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)", who);
+    return TGTC_OK;
+}
+
+static int latents_indexable(const char* who, int K, int64_t R, int64_t count) {
+    if (K * count >= kIndexLimit || K * R >= kIndexLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: K x count >= 2^31 (fewer latents per call)", who);
+    return TGTC_OK;
+}
+
+// The rule of the fp16x3+fp16mx pair without a plane (csrc/mlp_list_mx.hip): a fine handle in TGTC_PREC_FP16_FP6 and an
+// fp16x3 style handle with mx streams.
+static int list_mx_handles(const char* who, const tgtc_net* fine, const tgtc_net* style) {
+    if (fine->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the NeRF handle must be in fp16mx (the siblings without _mx take fp16x3 and fp16)", who);
+    if (style->precision != TGTC_PREC_FP16X3)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle must be in fp16x3 (an fp16 pair has no lo halves)", who);
+    if (!(style->mx && style->mx->dev))
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
+    return TGTC_OK;
+}
 }  // namespace tgtc
 
 using namespace tgtc;
@@ -193,7 +236,15 @@ extern "C" int tgtc_render_path(int request, int prec_coarse, int prec_fine, int
     return request;
 }
 
-// The depths-only instance of the plain ray kernel as an entry of its own: what the stylised chain, the multi-latent, the
+// ONE launch of the depths-only instance of the plain ray kernel (render_fused.hip): coarse depths -> coarse sigma -> weights ->
+// fine depths ts_out [R, n_coarse + n_fine], no image.  The caller has checked ray_kernel_built for the coarse precision.
+static int depths_only(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int n_coarse, int n_fine,
+                       float near_, float far_, const float* jitter, float* ts_out, void* stream) {
+    FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ts_out};
+    return launch_fused_depths(coarse->precision, a, as_stream(stream));
+}
+
+// That launch as an entry of its own: what the stylised chain, the multi-latent, the
 // culled and the restyle renders launch internally, and what lets a test hold a ray kernel's pixel against a reference
 // evaluated at the kernel's own fine depths (tests/test_ray_kernel_shapes_gpu.py).
 extern "C" int tgtc_render_depths(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
@@ -206,8 +257,7 @@ extern "C" int tgtc_render_depths(const tgtc_net* coarse, const double* rays_o, 
                     coarse->precision, n_coarse, n_fine);
     if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && ts_out, "render_depths: null pointer");
-    FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ts_out};
-    return launch_fused_depths(coarse->precision, a, as_stream(stream));
+    return depths_only(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ts_out, stream);
 }
 
 // ---- the per-ray stage between the passes: coarse densities -> weights -> fine depths
@@ -225,6 +275,23 @@ static int coarse_to_fine(const float* rgb_c, const float* sigma_c, const float*
     const int rc = launch_composite(rgb_c, sigma_c, ts_c, R, n_coarse, rgb_coarse, t_coarse, w_c, st);
     if (rc) return rc;
     return launch_sample_fine(rays_o, rays_d, ts_c, w_c, R, n_coarse, n_fine, nullptr, ts_f, st);
+}
+
+// The geometry half of a stylised render that wants no coarse image: the fine depths ws.ts_f from the coarse net alone.
+// Where the plain ray kernel is built for the coarse precision it is that kernel's first half (coarse depths -> coarse
+// sigma -> weights -> fine depths, which never leave the kernel: ws.ts_c / sigma_c / w_c stay unwritten); otherwise coarse
+// depths, the sigma-only NeRF launch and the per-ray stage above.  WS: any workspace with ts_c, sigma_c, w_c and ts_f.
+template <class WS>
+static int fine_depths(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int n_coarse, int n_fine,
+                       float near_, float far_, const float* jitter, const WS& ws, void* stream) {
+    hipStream_t st = as_stream(stream);
+    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0))
+        return depths_only(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws.ts_f, stream);
+    int rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
+    if (rc) return rc;
+    rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
+    if (rc) return rc;
+    return coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
 }
 
 // ---- the two-phase fine pass of the plain chain
@@ -378,24 +445,23 @@ extern "C" int tgtc_render_rays_styled(const tgtc_net* coarse, const tgtc_net* f
                  ws.total);
     hipStream_t st = as_stream(stream);
     int rc;
-    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, want_coarse)) {
-        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
-        rc = launch_fused_depths(coarse->precision, a, st);
+    if (!want_coarse) {
+        rc = fine_depths(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws, stream);
+    } else {
+        // the coarse image: the stylised colours on the coarse pass too (the depth image alone needs sigma only), and the
+        // compositor between the passes
+        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
         if (rc) return rc;
-        rc = styled_forward_rays_impl(fine, style, rays_o, rays_d, ws.ts_f, z, R, n_coarse + n_fine, ws.rgb_f, ws.sigma_f, st);
+        float* rgb_c = rgb_coarse ? ws.rgb_c : nullptr;
+        if (rgb_c)
+            rc = styled_forward_rays_impl(coarse, style, rays_o, rays_d, ws.ts_c, z, R, n_coarse, rgb_c, ws.sigma_c, st);
+        else
+            rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
         if (rc) return rc;
-        return launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, n_coarse + n_fine, rgb_fine, t_fine, nullptr, st);
+        rc = coarse_to_fine(rgb_c, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, rgb_coarse, t_coarse, ws.ts_f, st);
     }
-    rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
     if (rc) return rc;
-    float* rgb_c = rgb_coarse ? ws.rgb_c : nullptr;
-    if (rgb_c)
-        rc = styled_forward_rays_impl(coarse, style, rays_o, rays_d, ws.ts_c, z, R, n_coarse, rgb_c, ws.sigma_c, st);
-    else
-        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
-    if (rc) return rc;
-    rc = coarse_to_fine(rgb_c, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, rgb_coarse, t_coarse, ws.ts_f, st);
-    if (rc) return rc;
+    // styled fine pass + composite
     rc = styled_forward_rays_impl(fine, style, rays_o, rays_d, ws.ts_f, z, R, n_coarse + n_fine, ws.rgb_f, ws.sigma_f, st);
     if (rc) return rc;
     return launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, n_coarse + n_fine, rgb_fine, t_fine, nullptr, st);
@@ -418,31 +484,19 @@ extern "C" int tgtc_render_rays_styled_multi(const tgtc_net* coarse, const tgtc_
     TGTC_REQUIRE(K >= 1, "render_rays_styled_multi: need K >= 1 latent sets (got %d)", K);
     TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
                  "render_rays_styled_multi: coarse and fine must be NeRF handles, style a style handle");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
+    if (const int rc = sample_counts(n_coarse, n_fine)) return rc;
     TGTC_REQUIRE(fine->precision == style->precision,
                  "render_rays_styled_multi: fine NeRF and style nets were packed with different precisions");
     if (R == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_multi: null pointer");
     const int nt = n_coarse + n_fine;
-    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_multi: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    if (const int rc = colours_indexable("render_rays_styled_multi", K, R, nt)) return rc;
     MultiWorkspace ws(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
     TGTC_REQUIRE(workspace_bytes >= ws.total, "render_rays_styled_multi: workspace of %zu bytes, need %zu", workspace_bytes,
                  ws.total);
     hipStream_t st = as_stream(stream);
-    int rc;
-    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
-        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
-        rc = launch_fused_depths(coarse->precision, a, st);
-        if (rc) return rc;
-    } else {
-        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
-        if (rc) return rc;
-        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
-        if (rc) return rc;
-        rc = coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
-        if (rc) return rc;
-    }
+    int rc = fine_depths(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws, stream);
+    if (rc) return rc;
     rc = styled_forward_rays_multi_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, ws.rgb_f, ws.sigma_f, st);
     if (rc) return rc;
     for (int k = 0; k < K; ++k) {
@@ -467,20 +521,9 @@ static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const doub
     const MultiWorkspace& ws = sw.m;
     const int nt = n_coarse + n_fine;
     hipStream_t st = as_stream(stream);
-    int rc;
     // 1. geometry half, as tgtc_render_rays_styled_multi
-    if (ray_kernel_built(coarse->precision, coarse->precision, -1, n_coarse, n_fine, 0)) {
-        FusedArgs a{rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, coarse->dev, coarse->dev, nullptr, nullptr, ws.ts_f};
-        rc = launch_fused_depths(coarse->precision, a, st);
-        if (rc) return rc;
-    } else {
-        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
-        if (rc) return rc;
-        rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, nullptr, ws.sigma_c, st);
-        if (rc) return rc;
-        rc = coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
-        if (rc) return rc;
-    }
+    int rc = fine_depths(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws, stream);
+    if (rc) return rc;
     // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
     //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
     rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
@@ -496,37 +539,55 @@ static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const doub
 // min_weight: geometry half as above, a sigma-only pass of the fine NeRF over every sample, the existing compositing kernel
 // for depth + weights, the compaction, then the indexed multi-latent kernel (mlp_style_sparse.hip) into zero-filled colour
 // planes and K compositing launches over the shared sigma / depths.
-extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
-                                              const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
-                                              int n_coarse, int n_fine, float near_, float far_, const float* jitter,
-                                              float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
-                                              float* t_fine, uint32_t* live_count, void* stream) {
-    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse: need K >= 1 latent sets (got %d)", K);
-    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse: min_weight must be >= 0 and not NaN (got %g)", (double)min_weight);
-    TGTC_REQUIRE(coarse && fine && style && R >= 0, "render_rays_styled_sparse: bad argument");
-    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
-                 "render_rays_styled_sparse: coarse and fine must be NeRF handles, style a style handle");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    TGTC_REQUIRE(fine->precision == style->precision,
-                 "render_rays_styled_sparse: fine NeRF and style nets were packed with different precisions");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse: null pointer");
+//
+// The body of the three tgtc_render_rays_styled_sparse* entries.  flags: 0 is the per-ray form, z [K,R,32]; kFold the
+// frame-constant one, z [K,32] folded into K bias tables in one more plane at the end of the workspace; kFold | kMx that
+// for the fp16x3+fp16mx pair.  They differ in the rule for the handles' precisions and in the list launch, nothing else.
+static int render_rays_culled(const char* who, unsigned flags, const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                              const double* rays_o, const double* rays_d, const float* z, int K, int64_t R, int n_coarse,
+                              int n_fine, float near_, float far_, const float* jitter, float min_weight, void* workspace,
+                              size_t workspace_bytes, float* rgb_fine, float* t_fine, uint32_t* live_count, void* stream) {
+    const bool fold = flags & kFold, mx = flags & kMx;
+    TGTC_REQUIRE(K >= 1, "%s: need K >= 1 %s (got %d)", who, fold ? "latents" : "latent sets", K);
+    TGTC_REQUIRE(min_weight >= 0.0f, "%s: min_weight must be >= 0 and not NaN (got %g)", who, (double)min_weight);
+    TGTC_REQUIRE(R >= 0, "%s: bad argument", who);
+    if (const int rc = sample_counts(n_coarse, n_fine)) return rc;
+    // (the checks that need no handle come first: they can be exercised without a device)
     const int nt = n_coarse + n_fine;
-    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+    if (const int rc = colours_indexable(who, K, R, nt)) return rc;
+    TGTC_REQUIRE(coarse && fine && style, "%s: null handle", who);
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
+                 "%s: coarse and fine must be NeRF handles, style a style handle", who);
+    if (mx) {
+        if (const int rc = list_mx_handles(who, fine, style)) return rc;
+    } else {
+        TGTC_REQUIRE(fine->precision == style->precision, "%s: fine NeRF and style nets were packed with different precisions", who);
+    }
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "%s: null pointer", who);
     SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
-    TGTC_REQUIRE(workspace_bytes >= sw.total, "render_rays_styled_sparse: workspace of %zu bytes, need %zu", workspace_bytes,
-                 sw.total);
+    const size_t need = sw.total + (fold ? align256(tgtc_style_folded_bytes(K)) : 0);
+    TGTC_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, need %zu", who, workspace_bytes, need);
+    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + sw.total);
     const MultiWorkspace& ws = sw.m;
     hipStream_t st = as_stream(stream);
+    int rc;
+    // 0. the K bias tables
+    if (fold) {
+        rc = style_fold_latents_impl(style, z, K, folded, st);
+        if (rc) return rc;
+    }
     // 1-4. everything that depends on the ray alone
-    int rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine,
-                          live_count, stream);
+    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
+                      stream);
     if (rc) return rc;
     // 5. dead samples keep colour +0
     TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
-    // 6. trunk + concat MLP + style MLP over the list
-    rc = styled_forward_rays_sparse_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    // 6. over the list (the host never learns its length): trunk + concat MLP + style MLP, their folded forms, or the
+    //    fp16mx trunk + the folded style pair's fp16mx streams
+    if (mx) rc = styled_forward_list_folded_mx_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    else if (fold) rc = styled_forward_list_folded_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
+    else rc = styled_forward_rays_sparse_impl(fine, style, rays_o, rays_d, ws.ts_f, z, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
     if (rc) return rc;
     // 7. compositing over the shared sigma / depths
     for (int k = 0; k < K; ++k) {
@@ -535,6 +596,15 @@ extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc
         if (rc) return rc;
     }
     return TGTC_OK;
+}
+
+extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                              const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                              int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                              float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                              float* t_fine, uint32_t* live_count, void* stream) {
+    return render_rays_culled("render_rays_styled_sparse", 0, coarse, fine, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, near_,
+                              far_, jitter, min_weight, workspace, workspace_bytes, rgb_fine, t_fine, live_count, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ geometry cache + restyle
@@ -593,34 +663,70 @@ extern "C" size_t tgtc_restyle_workspace_bytes(int64_t count, int K) {
     return align256((size_t)K * (size_t)count * 3 * sizeof(float));
 }
 
-extern "C" int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
-                                 const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
-                                 size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine,
-                                 float* t_fine, void* stream) {
-    TGTC_REQUIRE(K >= 1, "restyle_rays: need K >= 1 latent sets (got %d)", K);
-    TGTC_REQUIRE(fine && style && R >= 0 && count >= 0, "restyle_rays: bad argument");
-    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays: fine must be a NeRF handle, style a style handle");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    TGTC_REQUIRE(fine->precision == style->precision,
-                 "restyle_rays: fine NeRF and style nets were packed with different precisions");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays: null pointer");
+extern "C" size_t tgtc_restyle_folded_workspace_bytes(int64_t count, int K) {
+    if (count < 0 || K < 1) return 0;
+    return tgtc_restyle_workspace_bytes(count, K) + align256(tgtc_style_folded_bytes(K));
+}
+
+// The body of the six tgtc_restyle_rays* entries: one style launch over the cached list into the compact colour planes, one
+// compositing launch over (latent, ray), the depth copy.  flags: kFold as in render_rays_culled; kPlane reads the fine NeRF
+// trunk from the plane of tgtc_geometry_trunk (below) and takes no NeRF handle (fine is not looked at), the other forms
+// take no plane (trunk is not looked at); kMx runs the style networks on the handle's fp16mx streams -- from the plane, or
+// behind an fp16mx fine handle -- and exists folded only.  The forms differ in the rule for the handles and in the style launch.
+static int restyle_rays(const char* who, unsigned flags, const tgtc_net* fine, const tgtc_net* style, const double* rays_o,
+                        const double* rays_d, const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                        size_t cache_bytes, int64_t count, const void* trunk, size_t trunk_bytes, void* workspace,
+                        size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream) {
+    const bool fold = flags & kFold, mx = flags & kMx, plane = flags & kPlane;
+    TGTC_REQUIRE(K >= 1, "%s: need K >= 1 %s (got %d)", who, fold || plane ? "latents" : "latent sets", K);
+    TGTC_REQUIRE(R >= 0 && count >= 0, "%s: bad argument", who);
+    if (const int rc = sample_counts(n_coarse, n_fine)) return rc;
+    // (the checks that need no handle come first: they can be exercised without a device)
     const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(count <= R * nt, "restyle_rays: count %lld exceeds the %lld samples", (long long)count, (long long)(R * nt));
-    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays: K x count >= 2^31 (fewer latents per call)");
+    if (const int rc = samples_indexable(who, R, nt)) return rc;
+    TGTC_REQUIRE(count <= R * nt || R == 0, "%s: count %lld exceeds the %lld samples", who, (long long)count, (long long)(R * nt));
+    if (const int rc = latents_indexable(who, K, R, count)) return rc;
+    TGTC_REQUIRE(style && (plane || fine), "%s: null handle", who);
+    if (plane) {
+        TGTC_REQUIRE(style->kind == 1, "%s: style must be a style handle", who);
+        if (mx && !(style->mx && style->mx->dev))
+            return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
+    } else {
+        TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "%s: fine must be a NeRF handle, style a style handle", who);
+        if (mx) {
+            if (const int rc = list_mx_handles(who, fine, style)) return rc;
+        } else {
+            TGTC_REQUIRE(fine->precision == style->precision, "%s: fine NeRF and style nets were packed with different precisions", who);
+        }
+    }
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0) && (!plane || trunk || count == 0),
+                 "%s: null pointer", who);
     GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays: cache of %zu bytes, need %zu", cache_bytes, gc.total);
-    const size_t need = tgtc_restyle_workspace_bytes(count, K);
-    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "%s: cache of %zu bytes, need %zu", who, cache_bytes, gc.total);
+    if (plane) {
+        const size_t need_plane = tgtc_geometry_trunk_bytes(style->precision, count);
+        TGTC_REQUIRE(trunk_bytes >= need_plane, "%s: plane of %zu bytes, need %zu", who, trunk_bytes, need_plane);
+    }
+    const size_t need = fold ? tgtc_restyle_folded_workspace_bytes(count, K) : tgtc_restyle_workspace_bytes(count, K);
+    TGTC_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, need %zu", who, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     float* rgb_live = static_cast<float*>(workspace);
     int rc;
-    // 1. trunk + concat MLP + style MLP over the cached list into the compact colour planes (nothing to launch for an empty list)
+    // 1. (the K bias tables, then) the trunk -- computed, or base_remap from the plane -- + concat MLP + style MLP over the
+    //    cached list (nothing to launch for an empty list)
     if (count > 0) {
-        rc = styled_restyle_live_impl(fine, style, rays_o, rays_d, z, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        float* folded = nullptr;
+        if (fold) {
+            folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
+            rc = style_fold_latents_impl(style, z, K, folded, st);
+            if (rc) return rc;
+        }
+        if (plane && mx) rc = styled_restyle_plane_mx_impl(style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
+        else if (plane) rc = styled_restyle_plane_impl(style, rays_o, rays_d, z, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
+        else if (mx) rc = styled_restyle_live_folded_mx_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        else if (fold) rc = styled_restyle_live_folded_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
+        else rc = styled_restyle_live_impl(fine, style, rays_o, rays_d, z, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
         if (rc) return rc;
     }
     // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
@@ -631,27 +737,46 @@ extern "C" int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, co
     return TGTC_OK;
 }
 
+extern "C" int tgtc_restyle_rays(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
+                                 const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
+                                 size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                 float* t_fine, void* stream) {
+    return restyle_rays("restyle_rays", 0, fine, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes, count, nullptr,
+                        0, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+}
+
 // ------------------------------------------------------------------------------------------------ frame-constant latents
 // The culled render and the restyle for latents that do not depend on the ray: z [K,32].  The latent k-step of every layer
 // of the two style networks is folded into K bias tables (tgtc_style_fold_latents, mlp_style.hip) kept in one more plane
 // at the end of the workspace, and the folded instances of the indexed kernels (mlp_style_sparse.hip) run on the streams
-// packed without that k-step.  Everything else is the unfolded sibling's.
+// packed without that k-step.  Everything else is the unfolded sibling's (kFold of the shared bodies).
+
+// The folded list launch as an entry of its own, and (kMx) its form for the fp16x3+fp16mx pair.
+static int styled_forward_list_folded(const char* who, unsigned flags, const tgtc_net* nerf, const tgtc_net* style,
+                                      const double* rays_o, const double* rays_d, const float* ts, const void* folded, int K,
+                                      int64_t R, int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
+    TGTC_REQUIRE(K >= 1, "%s: need K >= 1 latents (got %d)", who, K);
+    TGTC_REQUIRE(R >= 0 && N >= 1, "%s: bad argument", who);
+    if (R >= kIndexLimit || R * (int64_t)N >= kIndexLimit || R * (int64_t)N * K >= kIndexLimit)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: K x R x N >= 2^31 in one launch (chunk the rays)", who);
+    TGTC_REQUIRE(nerf && style, "%s: null handle", who);
+    TGTC_REQUIRE(nerf->kind == 0 && style->kind == 1, "%s: nerf must be a NeRF handle, style a style handle", who);
+    if (flags & kMx) {
+        if (const int rc = list_mx_handles(who, nerf, style)) return rc;
+    } else {
+        TGTC_REQUIRE(nerf->precision == style->precision, "%s: NeRF and style nets were packed with different precisions", who);
+    }
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && folded && live && n_live && rgb, "%s: null pointer", who);
+    return (flags & kMx ? styled_forward_list_folded_mx_impl : styled_forward_list_folded_impl)(
+        nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live, rgb, as_stream(stream));
+}
 
 extern "C" int tgtc_styled_forward_list_folded(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o,
                                                const double* rays_d, const float* ts, const void* folded, int K, int64_t R,
                                                int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
-    TGTC_REQUIRE(K >= 1, "styled_forward_list_folded: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(R >= 0 && N >= 1, "styled_forward_list_folded: bad argument");
-    constexpr int64_t kLimit = (int64_t)1 << 31;
-    if (R >= kLimit || R * (int64_t)N >= kLimit || R * (int64_t)N * K >= kLimit)
-        return fail(TGTC_ERR_UNSUPPORTED, "styled_forward_list_folded: K x R x N >= 2^31 in one launch (chunk the rays)");
-    TGTC_REQUIRE(nerf && style, "styled_forward_list_folded: null handle");
-    TGTC_REQUIRE(nerf->kind == 0 && style->kind == 1, "styled_forward_list_folded: nerf must be a NeRF handle, style a style handle");
-    TGTC_REQUIRE(nerf->precision == style->precision,
-                 "styled_forward_list_folded: NeRF and style nets were packed with different precisions");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && ts && folded && live && n_live && rgb, "styled_forward_list_folded: null pointer");
-    return styled_forward_list_folded_impl(nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live, rgb, as_stream(stream));
+    return styled_forward_list_folded("styled_forward_list_folded", 0, nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live,
+                                      rgb, stream);
 }
 
 extern "C" size_t tgtc_render_styled_sparse_folded_workspace_bytes(int64_t R, int n_coarse, int n_fine, int K) {
@@ -665,97 +790,17 @@ extern "C" int tgtc_render_rays_styled_sparse_folded(const tgtc_net* coarse, con
                                                      const float* jitter, float min_weight, void* workspace,
                                                      size_t workspace_bytes, float* rgb_fine, float* t_fine,
                                                      uint32_t* live_count, void* stream) {
-    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse_folded: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse_folded: min_weight must be >= 0 and not NaN (got %g)",
-                 (double)min_weight);
-    TGTC_REQUIRE(R >= 0, "render_rays_styled_sparse_folded: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse_folded: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(coarse && fine && style, "render_rays_styled_sparse_folded: null handle");
-    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
-                 "render_rays_styled_sparse_folded: coarse and fine must be NeRF handles, style a style handle");
-    TGTC_REQUIRE(fine->precision == style->precision,
-                 "render_rays_styled_sparse_folded: fine NeRF and style nets were packed with different precisions");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse_folded: null pointer");
-    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
-    const size_t need = sw.total + align256(tgtc_style_folded_bytes(K));
-    TGTC_REQUIRE(workspace_bytes >= need, "render_rays_styled_sparse_folded: workspace of %zu bytes, need %zu", workspace_bytes, need);
-    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + sw.total);
-    const MultiWorkspace& ws = sw.m;
-    hipStream_t st = as_stream(stream);
-    // 0. the K bias tables
-    int rc = style_fold_latents_impl(style, z, K, folded, st);
-    if (rc) return rc;
-    // 1-4. everything that depends on the ray alone
-    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
-                      stream);
-    if (rc) return rc;
-    // 5. dead samples keep colour +0
-    TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
-    // 6. trunk + folded concat MLP + folded style MLP over the list
-    rc = styled_forward_list_folded_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
-    if (rc) return rc;
-    // 7. compositing over the shared sigma / depths
-    for (int k = 0; k < K; ++k) {
-        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, nullptr,
-                              nullptr, st);
-        if (rc) return rc;
-    }
-    return TGTC_OK;
-}
-
-extern "C" size_t tgtc_restyle_folded_workspace_bytes(int64_t count, int K) {
-    if (count < 0 || K < 1) return 0;
-    return tgtc_restyle_workspace_bytes(count, K) + align256(tgtc_style_folded_bytes(K));
+    return render_rays_culled("render_rays_styled_sparse_folded", kFold, coarse, fine, style, rays_o, rays_d, z, K, R, n_coarse,
+                              n_fine, near_, far_, jitter, min_weight, workspace, workspace_bytes, rgb_fine, t_fine, live_count,
+                              stream);
 }
 
 extern "C" int tgtc_restyle_rays_folded(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
                                         const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
                                         size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes,
                                         float* rgb_fine, float* t_fine, void* stream) {
-    TGTC_REQUIRE(K >= 1, "restyle_rays_folded: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(R >= 0 && count >= 0, "restyle_rays_folded: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(count <= R * nt || R == 0, "restyle_rays_folded: count %lld exceeds the %lld samples", (long long)count,
-                 (long long)(R * nt));
-    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded: K x count >= 2^31 (fewer latents per call)");
-    TGTC_REQUIRE(fine && style, "restyle_rays_folded: null handle");
-    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays_folded: fine must be a NeRF handle, style a style handle");
-    TGTC_REQUIRE(fine->precision == style->precision,
-                 "restyle_rays_folded: fine NeRF and style nets were packed with different precisions");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays_folded: null pointer");
-    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays_folded: cache of %zu bytes, need %zu", cache_bytes, gc.total);
-    const size_t need = tgtc_restyle_folded_workspace_bytes(count, K);
-    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays_folded: workspace of %zu bytes, need %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    float* rgb_live = static_cast<float*>(workspace);
-    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
-    int rc;
-    // 1. the K bias tables, then trunk + folded concat MLP + folded style MLP over the cached list (nothing to launch for an
-    //    empty list)
-    if (count > 0) {
-        rc = style_fold_latents_impl(style, z, K, folded, st);
-        if (rc) return rc;
-        rc = styled_restyle_live_folded_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
-        if (rc) return rc;
-    }
-    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
-    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
-    if (rc) return rc;
-    // 3. the depth image
-    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return TGTC_OK;
+    return restyle_rays("restyle_rays_folded", kFold, fine, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes, count,
+                        nullptr, 0, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ restyle from a trunk plane
@@ -769,97 +814,65 @@ extern "C" size_t tgtc_geometry_trunk_bytes(int precision, int64_t count) {
     return (size_t)((count + per_tile - 1) / per_tile) * (size_t)131072;
 }
 
+// The body of tgtc_geometry_trunk and (mx) tgtc_geometry_trunk_mx: the same arguments and checks in the same order.  The
+// first takes an fp16x3 or fp16 handle and writes the plane of that precision; the second takes a handle in
+// TGTC_PREC_FP16_FP6 and writes the TGTC_PREC_FP16X3 plane (csrc/mlp_trunk_mx.hip).
+static int geometry_trunk(const char* who, bool mx, const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R,
+                          int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
+                          size_t trunk_bytes, void* stream) {
+    TGTC_REQUIRE(R >= 0 && count >= 0, "%s: bad argument", who);
+    if (const int rc = sample_counts(n_coarse, n_fine)) return rc;
+    // (the checks that need no handle come first: they can be exercised without a device)
+    const int nt = n_coarse + n_fine;
+    if (const int rc = samples_indexable(who, R, nt)) return rc;
+    TGTC_REQUIRE(count <= R * nt || R == 0, "%s: count %lld exceeds the %lld samples", who, (long long)count, (long long)(R * nt));
+    TGTC_REQUIRE(fine, "%s: null handle", who);
+    TGTC_REQUIRE(fine->kind == 0, "%s: fine must be a NeRF handle", who);
+    if (mx && fine->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: built for fp16mx handles only (tgtc_geometry_trunk takes fp16x3 and fp16)", who);
+    if (!mx && fine->precision != TGTC_PREC_FP16X3 && fine->precision != TGTC_PREC_FP16)
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style kernels are built for fp16x3 and fp16 handles only", who);
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && cache && (trunk || count == 0), "%s: null pointer", who);
+    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
+    TGTC_REQUIRE(cache_bytes >= gc.total, "%s: cache of %zu bytes, need %zu", who, cache_bytes, gc.total);
+    const size_t need = tgtc_geometry_trunk_bytes(mx ? TGTC_PREC_FP16X3 : fine->precision, count);
+    TGTC_REQUIRE(trunk_bytes >= need, "%s: plane of %zu bytes, need %zu", who, trunk_bytes, need);
+    if (count == 0) return TGTC_OK;
+    return (mx ? styled_trunk_plane_mx_impl : styled_trunk_plane_impl)(fine, rays_o, rays_d, R, nt, gc.live, gc.ts_live, count, trunk,
+                                                                       as_stream(stream));
+}
+
 extern "C" int tgtc_geometry_trunk(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
                                    int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
                                    size_t trunk_bytes, void* stream) {
-    TGTC_REQUIRE(R >= 0 && count >= 0, "geometry_trunk: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(count <= R * nt || R == 0, "geometry_trunk: count %lld exceeds the %lld samples", (long long)count,
-                 (long long)(R * nt));
-    TGTC_REQUIRE(fine, "geometry_trunk: null handle");
-    TGTC_REQUIRE(fine->kind == 0, "geometry_trunk: fine must be a NeRF handle");
-    if (fine->precision != TGTC_PREC_FP16X3 && fine->precision != TGTC_PREC_FP16)
-        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk: the style kernels are built for fp16x3 and fp16 handles only");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && cache && (trunk || count == 0), "geometry_trunk: null pointer");
-    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "geometry_trunk: cache of %zu bytes, need %zu", cache_bytes, gc.total);
-    const size_t need = tgtc_geometry_trunk_bytes(fine->precision, count);
-    TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk: plane of %zu bytes, need %zu", trunk_bytes, need);
-    if (count == 0) return TGTC_OK;
-    return styled_trunk_plane_impl(fine, rays_o, rays_d, R, nt, gc.live, gc.ts_live, count, trunk, as_stream(stream));
+    return geometry_trunk("geometry_trunk", false, fine, rays_o, rays_d, R, n_coarse, n_fine, cache, cache_bytes, count, trunk,
+                          trunk_bytes, stream);
 }
 
-// tgtc_restyle_rays / tgtc_restyle_rays_folded with the trunk read from the plane: the same workspaces, the same compositing
-// launch and depth copy behind another style launch.
-static int restyle_rays_trunk(const char* who, bool fold, bool mx, const tgtc_net* style, const double* rays_o, const double* rays_d,
-                              const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
-                              int64_t count, const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
-                              float* rgb_fine, float* t_fine, void* stream) {
-    TGTC_REQUIRE(K >= 1, "%s: need K >= 1 latents (got %d)", who, K);
-    TGTC_REQUIRE(R >= 0 && count >= 0, "%s: bad argument", who);
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31)) return fail(TGTC_ERR_UNSUPPORTED, "%s: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)", who);
-    TGTC_REQUIRE(count <= R * nt || R == 0, "%s: count %lld exceeds the %lld samples", who, (long long)count, (long long)(R * nt));
-    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "%s: K x count >= 2^31 (fewer latents per call)", who);
-    TGTC_REQUIRE(style, "%s: null handle", who);
-    TGTC_REQUIRE(style->kind == 1, "%s: style must be a style handle", who);
-    if (mx && !(style->mx && style->mx->dev))
-        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0) && (trunk || count == 0),
-                 "%s: null pointer", who);
-    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "%s: cache of %zu bytes, need %zu", who, cache_bytes, gc.total);
-    const size_t need_plane = tgtc_geometry_trunk_bytes(style->precision, count);
-    TGTC_REQUIRE(trunk_bytes >= need_plane, "%s: plane of %zu bytes, need %zu", who, trunk_bytes, need_plane);
-    const size_t need = fold ? tgtc_restyle_folded_workspace_bytes(count, K) : tgtc_restyle_workspace_bytes(count, K);
-    TGTC_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, need %zu", who, workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    float* rgb_live = static_cast<float*>(workspace);
-    int rc;
-    // 1. (the K bias tables, then) concat MLP + style MLP over the cached list, base_remap from the plane (nothing to launch
-    //    for an empty list)
-    if (count > 0) {
-        float* folded = nullptr;
-        if (fold) {
-            folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
-            rc = style_fold_latents_impl(style, z, K, folded, st);
-            if (rc) return rc;
-        }
-        if (mx) rc = styled_restyle_plane_mx_impl(style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
-        else rc = styled_restyle_plane_impl(style, rays_o, rays_d, z, folded, K, R, nt, gc.live, gc.ts_live, count, trunk, rgb_live, st);
-        if (rc) return rc;
-    }
-    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
-    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
-    if (rc) return rc;
-    // 3. the depth image
-    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return TGTC_OK;
+extern "C" int tgtc_geometry_trunk_mx(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
+                                      int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
+                                      size_t trunk_bytes, void* stream) {
+    return geometry_trunk("geometry_trunk_mx", true, fine, rays_o, rays_d, R, n_coarse, n_fine, cache, cache_bytes, count, trunk,
+                          trunk_bytes, stream);
 }
 
+// tgtc_restyle_rays / tgtc_restyle_rays_folded with the trunk read from the plane (kPlane of restyle_rays): the same
+// workspaces, the same compositing launch and depth copy behind another style launch.
 extern "C" int tgtc_restyle_rays_trunk(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z, int K,
                                        int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes, int64_t count,
                                        const void* trunk, size_t trunk_bytes, void* workspace, size_t workspace_bytes,
                                        float* rgb_fine, float* t_fine, void* stream) {
-    return restyle_rays_trunk("restyle_rays_trunk", false, false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes,
-                              count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+    return restyle_rays("restyle_rays_trunk", kPlane, nullptr, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache, cache_bytes,
+                        count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
 extern "C" int tgtc_restyle_rays_trunk_folded(const tgtc_net* style, const double* rays_o, const double* rays_d, const float* z,
                                               int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
                                               int64_t count, const void* trunk, size_t trunk_bytes, void* workspace,
                                               size_t workspace_bytes, float* rgb_fine, float* t_fine, void* stream) {
-    return restyle_rays_trunk("restyle_rays_trunk_folded", true, false, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
-                              cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
+    return restyle_rays("restyle_rays_trunk_folded", kPlane | kFold, nullptr, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
+                        cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
 // ... and with the style networks in fp16mx: the folded form on the handle's mx streams (tgtc_style_enable_mx; an fp16x3 handle,
@@ -869,36 +882,8 @@ extern "C" int tgtc_restyle_rays_trunk_folded_mx(const tgtc_net* style, const do
                                                  size_t cache_bytes, int64_t count, const void* trunk, size_t trunk_bytes,
                                                  void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
                                                  void* stream) {
-    return restyle_rays_trunk("restyle_rays_trunk_folded_mx", true, true, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
-                              cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ the plane from an fp16mx handle
-// tgtc_geometry_trunk's arguments and checks in its order; the handle is in TGTC_PREC_FP16_FP6 and the plane it writes is the
-// TGTC_PREC_FP16X3 plane (csrc/mlp_trunk_mx.hip)
-extern "C" int tgtc_geometry_trunk_mx(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int n_coarse,
-                                      int n_fine, const void* cache, size_t cache_bytes, int64_t count, void* trunk,
-                                      size_t trunk_bytes, void* stream) {
-    TGTC_REQUIRE(R >= 0 && count >= 0, "geometry_trunk_mx: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk_mx: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(count <= R * nt || R == 0, "geometry_trunk_mx: count %lld exceeds the %lld samples", (long long)count,
-                 (long long)(R * nt));
-    TGTC_REQUIRE(fine, "geometry_trunk_mx: null handle");
-    TGTC_REQUIRE(fine->kind == 0, "geometry_trunk_mx: fine must be a NeRF handle");
-    if (fine->precision != TGTC_PREC_FP16_FP6)
-        return fail(TGTC_ERR_UNSUPPORTED, "geometry_trunk_mx: built for fp16mx handles only (tgtc_geometry_trunk takes fp16x3 and fp16)");
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && cache && (trunk || count == 0), "geometry_trunk_mx: null pointer");
-    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "geometry_trunk_mx: cache of %zu bytes, need %zu", cache_bytes, gc.total);
-    const size_t need = tgtc_geometry_trunk_bytes(TGTC_PREC_FP16X3, count);
-    TGTC_REQUIRE(trunk_bytes >= need, "geometry_trunk_mx: plane of %zu bytes, need %zu", trunk_bytes, need);
-    if (count == 0) return TGTC_OK;
-    return styled_trunk_plane_mx_impl(fine, rays_o, rays_d, R, nt, gc.live, gc.ts_live, count, trunk, as_stream(stream));
+    return restyle_rays("restyle_rays_trunk_folded_mx", kPlane | kFold | kMx, nullptr, style, rays_o, rays_d, z, K, R, n_coarse,
+                        n_fine, cache, cache_bytes, count, trunk, trunk_bytes, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
 extern "C" int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t trunk_bytes, int64_t count, float* hi, float* lo,
@@ -918,32 +903,13 @@ extern "C" int tgtc_geometry_trunk_read(int precision, const void* trunk, size_t
 // The folded list entry points for a fine handle in TGTC_PREC_FP16_FP6 and an fp16x3 style handle with mx streams
 // (csrc/mlp_list_mx.hip: trunk and latents of a tile in one persistent kernel, base_remap parked in slab region B of the style
 // handle).  Arguments, workspaces, check order and the order of work are the siblings' (tgtc_styled_forward_list_folded,
-// tgtc_render_rays_styled_sparse_folded, tgtc_restyle_rays_folded); only the rule for the handles' precisions differs.
-static int list_mx_handles(const char* who, const tgtc_net* fine, const tgtc_net* style) {
-    if (fine->precision != TGTC_PREC_FP16_FP6)
-        return fail(TGTC_ERR_UNSUPPORTED, "%s: the NeRF handle must be in fp16mx (the siblings without _mx take fp16x3 and fp16)", who);
-    if (style->precision != TGTC_PREC_FP16X3)
-        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle must be in fp16x3 (an fp16 pair has no lo halves)", who);
-    if (!(style->mx && style->mx->dev))
-        return fail(TGTC_ERR_UNSUPPORTED, "%s: the style handle has no fp16mx streams (tgtc_style_enable_mx)", who);
-    return TGTC_OK;
-}
-
+// tgtc_render_rays_styled_sparse_folded, tgtc_restyle_rays_folded: kMx of the same bodies); only the rule for the handles'
+// precisions (list_mx_handles) and the launch differ.
 extern "C" int tgtc_styled_forward_list_folded_mx(const tgtc_net* nerf, const tgtc_net* style, const double* rays_o,
                                                   const double* rays_d, const float* ts, const void* folded, int K, int64_t R,
                                                   int N, const uint32_t* live, const uint32_t* n_live, float* rgb, void* stream) {
-    TGTC_REQUIRE(K >= 1, "styled_forward_list_folded_mx: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(R >= 0 && N >= 1, "styled_forward_list_folded_mx: bad argument");
-    constexpr int64_t kLimit = (int64_t)1 << 31;
-    if (R >= kLimit || R * (int64_t)N >= kLimit || R * (int64_t)N * K >= kLimit)
-        return fail(TGTC_ERR_UNSUPPORTED, "styled_forward_list_folded_mx: K x R x N >= 2^31 in one launch (chunk the rays)");
-    TGTC_REQUIRE(nerf && style, "styled_forward_list_folded_mx: null handle");
-    TGTC_REQUIRE(nerf->kind == 0 && style->kind == 1,
-                 "styled_forward_list_folded_mx: nerf must be a NeRF handle, style a style handle");
-    if (const int rc = list_mx_handles("styled_forward_list_folded_mx", nerf, style)) return rc;
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && ts && folded && live && n_live && rgb, "styled_forward_list_folded_mx: null pointer");
-    return styled_forward_list_folded_mx_impl(nerf, style, rays_o, rays_d, ts, folded, K, R, N, live, n_live, rgb, as_stream(stream));
+    return styled_forward_list_folded("styled_forward_list_folded_mx", kMx, nerf, style, rays_o, rays_d, ts, folded, K, R, N, live,
+                                      n_live, rgb, stream);
 }
 
 extern "C" int tgtc_render_rays_styled_sparse_folded_mx(const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
@@ -952,89 +918,16 @@ extern "C" int tgtc_render_rays_styled_sparse_folded_mx(const tgtc_net* coarse, 
                                                         const float* jitter, float min_weight, void* workspace,
                                                         size_t workspace_bytes, float* rgb_fine, float* t_fine,
                                                         uint32_t* live_count, void* stream) {
-    TGTC_REQUIRE(K >= 1, "render_rays_styled_sparse_folded_mx: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(min_weight >= 0.0f, "render_rays_styled_sparse_folded_mx: min_weight must be >= 0 and not NaN (got %g)",
-                 (double)min_weight);
-    TGTC_REQUIRE(R >= 0, "render_rays_styled_sparse_folded_mx: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R >= ((int64_t)1 << 31) || R * nt >= ((int64_t)1 << 31) || R * nt * K >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "render_rays_styled_sparse_folded_mx: K x R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(coarse && fine && style, "render_rays_styled_sparse_folded_mx: null handle");
-    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0 && style->kind == 1,
-                 "render_rays_styled_sparse_folded_mx: coarse and fine must be NeRF handles, style a style handle");
-    if (const int rc = list_mx_handles("render_rays_styled_sparse_folded_mx", fine, style)) return rc;
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && workspace && rgb_fine && t_fine, "render_rays_styled_sparse_folded_mx: null pointer");
-    SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, K);
-    const size_t need = sw.total + align256(tgtc_style_folded_bytes(K));
-    TGTC_REQUIRE(workspace_bytes >= need, "render_rays_styled_sparse_folded_mx: workspace of %zu bytes, need %zu", workspace_bytes,
-                 need);
-    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + sw.total);
-    const MultiWorkspace& ws = sw.m;
-    hipStream_t st = as_stream(stream);
-    // 0. the K bias tables
-    int rc = style_fold_latents_impl(style, z, K, folded, st);
-    if (rc) return rc;
-    // 1-4. everything that depends on the ray alone
-    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
-                      stream);
-    if (rc) return rc;
-    // 5. dead samples keep colour +0
-    TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
-    // 6. fp16mx trunk + the folded style pair's fp16mx streams over the list (the host never learns its length)
-    rc = styled_forward_list_folded_mx_impl(fine, style, rays_o, rays_d, ws.ts_f, folded, K, R, nt, sw.live, sw.scratch, ws.rgb_f, st);
-    if (rc) return rc;
-    // 7. compositing over the shared sigma / depths
-    for (int k = 0; k < K; ++k) {
-        rc = launch_composite(ws.rgb_f + (size_t)k * R * nt * 3, ws.sigma_f, ws.ts_f, R, nt, rgb_fine + (size_t)k * R * 3, nullptr,
-                              nullptr, st);
-        if (rc) return rc;
-    }
-    return TGTC_OK;
+    return render_rays_culled("render_rays_styled_sparse_folded_mx", kFold | kMx, coarse, fine, style, rays_o, rays_d, z, K, R,
+                              n_coarse, n_fine, near_, far_, jitter, min_weight, workspace, workspace_bytes, rgb_fine, t_fine,
+                              live_count, stream);
 }
 
 extern "C" int tgtc_restyle_rays_folded_mx(const tgtc_net* fine, const tgtc_net* style, const double* rays_o, const double* rays_d,
                                            const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache,
                                            size_t cache_bytes, int64_t count, void* workspace, size_t workspace_bytes,
                                            float* rgb_fine, float* t_fine, void* stream) {
-    TGTC_REQUIRE(K >= 1, "restyle_rays_folded_mx: need K >= 1 latents (got %d)", K);
-    TGTC_REQUIRE(R >= 0 && count >= 0, "restyle_rays_folded_mx: bad argument");
-    TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
-    // (the checks that need no handle come first: they can be exercised without a device)
-    const int nt = n_coarse + n_fine;
-    if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded_mx: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
-    TGTC_REQUIRE(count <= R * nt || R == 0, "restyle_rays_folded_mx: count %lld exceeds the %lld samples", (long long)count,
-                 (long long)(R * nt));
-    if (K * count >= ((int64_t)1 << 31) || K * R >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "restyle_rays_folded_mx: K x count >= 2^31 (fewer latents per call)");
-    TGTC_REQUIRE(fine && style, "restyle_rays_folded_mx: null handle");
-    TGTC_REQUIRE(fine->kind == 0 && style->kind == 1, "restyle_rays_folded_mx: fine must be a NeRF handle, style a style handle");
-    if (const int rc = list_mx_handles("restyle_rays_folded_mx", fine, style)) return rc;
-    if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && z && cache && rgb_fine && (workspace || count == 0), "restyle_rays_folded_mx: null pointer");
-    GeometryCacheLayout gc(static_cast<char*>(const_cast<void*>(cache)), R, count);
-    TGTC_REQUIRE(cache_bytes >= gc.total, "restyle_rays_folded_mx: cache of %zu bytes, need %zu", cache_bytes, gc.total);
-    const size_t need = tgtc_restyle_folded_workspace_bytes(count, K);
-    TGTC_REQUIRE(workspace_bytes >= need, "restyle_rays_folded_mx: workspace of %zu bytes, need %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
-    float* rgb_live = static_cast<float*>(workspace);
-    float* folded = reinterpret_cast<float*>(static_cast<char*>(workspace) + tgtc_restyle_workspace_bytes(count, K));
-    int rc;
-    // 1. the K bias tables, then fp16mx trunk + the folded style pair's fp16mx streams over the cached list (nothing to launch
-    //    for an empty list)
-    if (count > 0) {
-        rc = style_fold_latents_impl(style, z, K, folded, st);
-        if (rc) return rc;
-        rc = styled_restyle_live_folded_mx_impl(fine, style, rays_o, rays_d, folded, K, R, nt, gc.live, gc.ts_live, count, rgb_live, st);
-        if (rc) return rc;
-    }
-    // 2. every (latent, ray): the colour sums of the dense compositing kernel; a ray without live samples gets +0
-    rc = launch_composite_live(gc.ray_start, gc.live, gc.w_live, rgb_live, R, nt, K, count, rgb_fine, st);
-    if (rc) return rc;
-    // 3. the depth image
-    if (t_fine) TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, gc.t, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return TGTC_OK;
+    return restyle_rays("restyle_rays_folded_mx", kFold | kMx, fine, style, rays_o, rays_d, z, K, R, n_coarse, n_fine, cache,
+                        cache_bytes, count, nullptr, 0, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
+

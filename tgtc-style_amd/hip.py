@@ -84,6 +84,17 @@ _RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_flo
              "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t,
              "tgtc_style_folded_bytes": c_size_t, "tgtc_render_styled_sparse_folded_workspace_bytes": c_size_t,
              "tgtc_restyle_folded_workspace_bytes": c_size_t, "tgtc_geometry_trunk_bytes": c_size_t}
+# the argument lists that whole families of entry points share (include/tgtc_hip.h: "the sibling's arguments, one for one")
+_CULLED_RENDER = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_float,
+                  c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+_LIST_RESTYLE = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64,
+                 c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+_PLANE_RESTYLE = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p,
+                  c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+_TRUNK_BUILD = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p, c_size_t, c_void_p]
+_FOLDED_LIST = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                c_void_p]
+
 _OPTIONAL = {
     "tgtc_style_create": [ctypes.POINTER(Linear), c_int, ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],
     "tgtc_concat_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
@@ -99,49 +110,33 @@ _OPTIONAL = {
     "tgtc_render_rays_styled_multi": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                       c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
     "tgtc_render_styled_sparse_workspace_bytes": [c_int64, c_int, c_int, c_int],
-    "tgtc_render_rays_styled_sparse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
-                                       c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p,
-                                       c_void_p, c_void_p],
+    "tgtc_render_rays_styled_sparse": _CULLED_RENDER,
     "tgtc_geometry_build": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_float,
                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
     "tgtc_geometry_cache_bytes": [c_int64, c_int64],
     "tgtc_geometry_pack": [c_void_p, c_int64, c_int, c_int, c_float, c_int64, c_void_p, c_size_t, c_void_p],
     "tgtc_restyle_workspace_bytes": [c_int64, c_int],
-    "tgtc_restyle_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
-                          c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_restyle_rays": _LIST_RESTYLE,
     "tgtc_style_folded_bytes": [c_int],
     "tgtc_style_fold_latents": [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
-    "tgtc_styled_forward_list_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
-                                        c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_styled_forward_list_folded": _FOLDED_LIST,
     "tgtc_render_styled_sparse_folded_workspace_bytes": [c_int64, c_int, c_int, c_int],
-    "tgtc_render_rays_styled_sparse_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
-                                              c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p,
-                                              c_void_p, c_void_p, c_void_p],
+    "tgtc_render_rays_styled_sparse_folded": _CULLED_RENDER,
     "tgtc_restyle_folded_workspace_bytes": [c_int64, c_int],
-    "tgtc_restyle_rays_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
-                                 c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_restyle_rays_folded": _LIST_RESTYLE,
     "tgtc_geometry_trunk_bytes": [c_int, c_int64],
-    "tgtc_geometry_trunk": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p, c_size_t,
-                            c_void_p],
-    "tgtc_restyle_rays_trunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64,
-                                c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
-    "tgtc_restyle_rays_trunk_folded": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
-                                       c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_geometry_trunk": _TRUNK_BUILD,
+    "tgtc_restyle_rays_trunk": _PLANE_RESTYLE,
+    "tgtc_restyle_rays_trunk_folded": _PLANE_RESTYLE,
     "tgtc_style_enable_mx": [c_void_p, c_void_p],
     "tgtc_style_has_mx": [c_void_p],
     "tgtc_style_mx_read": [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t],
-    "tgtc_restyle_rays_trunk_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_size_t,
-                                          c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
-    "tgtc_geometry_trunk_mx": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_int64, c_void_p,
-                               c_size_t, c_void_p],
+    "tgtc_restyle_rays_trunk_folded_mx": _PLANE_RESTYLE,
+    "tgtc_geometry_trunk_mx": _TRUNK_BUILD,
     "tgtc_geometry_trunk_read": [c_int, c_void_p, c_size_t, c_int64, c_void_p, c_void_p, c_void_p],
-    "tgtc_styled_forward_list_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_void_p],
-    "tgtc_render_rays_styled_sparse_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
-                                                 c_int, c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t,
-                                                 c_void_p, c_void_p, c_void_p, c_void_p],
-    "tgtc_restyle_rays_folded_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
-                                    c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_styled_forward_list_folded_mx": _FOLDED_LIST,
+    "tgtc_render_rays_styled_sparse_folded_mx": _CULLED_RENDER,
+    "tgtc_restyle_rays_folded_mx": _LIST_RESTYLE,
 }
 
 

@@ -226,6 +226,39 @@ class RayRenderer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
+    @staticmethod
+    def _rays(rays_o, rays_d):
+        """rays_o, rays_d as contiguous float64, then the ray count and the device."""
+        rays_o = rays_o.to(torch.float64).contiguous()
+        rays_d = rays_d.to(torch.float64).contiguous()
+        return rays_o, rays_d, rays_o.shape[0], rays_o.device
+
+    @staticmethod
+    def _jitter(jitter):
+        return None if jitter is None else jitter.to(torch.float32).contiguous()
+
+    def _scratch(self, attr, need, device):
+        """The uint8 scratch tensor this renderer keeps under `attr`, grown to `need` bytes on `device`."""
+        ws = getattr(self, attr)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = None
+            setattr(self, attr, None)       # release the old one first: the two together may not fit
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+            setattr(self, attr, ws)
+        return ws
+
+    @staticmethod
+    def _check_zs(zs, R):
+        """zs [K,R,32] (per ray) or [K,32] (frame-constant: folded) as contiguous float32, then K and whether it is folded."""
+        zs = zs.to(torch.float32).contiguous()
+        folded = zs.dim() == 2
+        if folded:
+            if zs.shape[0] < 1 or zs.shape[1] != 32:
+                raise ValueError("zs must be [K,32] with K >= 1, got %s" % list(zs.shape))
+        elif zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
+            raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
+        return zs, zs.shape[0], folded
+
     def render(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, z=None, want_coarse=False,
                min_weight=None):
         """rays_o, rays_d float64 [R,3] on the GPU -> dict rgb [R,3], t [R] (+ rgb_coarse, t_coarse).
@@ -245,9 +278,7 @@ class RayRenderer:
         lib = hip.load()
         if n_fine <= 0:
             raise ValueError("N_samples_fine must be > 0 (the reference render paths dereference None otherwise)")
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
-        R, dev = rays_o.shape[0], rays_o.device
+        rays_o, rays_d, R, dev = self._rays(rays_o, rays_d)
         plain = self.style is None or z is None
         path = self._path(n_coarse, n_fine, styled=not plain, want_coarse=want_coarse)
         if path < 0:
@@ -259,8 +290,7 @@ class RayRenderer:
         t = torch.empty(R, device=dev, dtype=torch.float32)
         rgb_c = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_coarse else None
         t_c = torch.empty(R, device=dev, dtype=torch.float32) if want_coarse else None
-        if jitter is not None:
-            jitter = jitter.to(torch.float32).contiguous()
+        jitter = self._jitter(jitter)
         rest = (path, hip.ptr(ws), 0 if ws is None else ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(rgb_c), hip.ptr(t_c),
                    hip.stream())
         if plain:
@@ -285,12 +315,9 @@ class RayRenderer:
         handle evaluates its fine pass at: the depths-only instance of the plain ray kernel (tgtc_render_depths), one launch,
         no workspace.  ValueError where no such kernel is built (sample counts, or a coarse handle in fp16mx)."""
         hip.require_gpu(rays_o, rays_d)
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
-        R = rays_o.shape[0]
-        ts = torch.empty(R, n_coarse + n_fine, device=rays_o.device, dtype=torch.float32)
-        if jitter is not None:
-            jitter = jitter.to(torch.float32).contiguous()
+        rays_o, rays_d, R, dev = self._rays(rays_o, rays_d)
+        ts = torch.empty(R, n_coarse + n_fine, device=dev, dtype=torch.float32)
+        jitter = self._jitter(jitter)
         rc = hip.load().tgtc_render_depths(self.coarse.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), R, n_coarse, n_fine,
                                            float(near), float(far), hip.ptr(jitter), hip.ptr(ts), hip.stream())
         if rc == -2:       # TGTC_ERR_UNSUPPORTED
@@ -345,17 +372,8 @@ class RayRenderer:
             raise ValueError("render_latents needs a style pair and zs [K,R,32] or [K,32]")
         if n_fine <= 0:
             raise ValueError("N_samples_fine must be > 0 (the reference render paths dereference None otherwise)")
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
-        R, dev = rays_o.shape[0], rays_o.device
-        zs = zs.to(torch.float32).contiguous()
-        folded = zs.dim() == 2
-        if folded:
-            if zs.shape[0] < 1 or zs.shape[1] != 32:
-                raise ValueError("zs must be [K,32] with K >= 1, got %s" % list(zs.shape))
-        elif zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
-            raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
-        K = zs.shape[0]
+        rays_o, rays_d, R, dev = self._rays(rays_o, rays_d)
+        zs, K, folded = self._check_zs(zs, R)
         if min_weight is not None:
             min_weight = float(min_weight)
             if not min_weight >= 0:
@@ -364,14 +382,10 @@ class RayRenderer:
                     lib.tgtc_render_styled_sparse_workspace_bytes)(R, n_coarse, n_fine, K)
         else:
             need = lib.tgtc_render_styled_multi_workspace_bytes(R, n_coarse, n_fine, K)
-        if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
-            self._ws_multi = None       # release the old one first: the two together may not fit
-            self._ws_multi = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        ws = self._ws_multi
+        ws = self._scratch("_ws_multi", need, dev)
         rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
-        if jitter is not None:
-            jitter = jitter.to(torch.float32).contiguous()
+        jitter = self._jitter(jitter)
         if min_weight is not None:
             live = torch.zeros((), device=dev, dtype=torch.int32)
             call = lib.tgtc_render_rays_styled_sparse_folded if folded else lib.tgtc_render_rays_styled_sparse
@@ -402,16 +416,9 @@ class RayRenderer:
         min_weight = float(min_weight)
         if not min_weight >= 0:
             raise ValueError("min_weight must be >= 0 (got %r)" % min_weight)
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
-        R, dev = rays_o.shape[0], rays_o.device
-        need = lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, 1)
-        if self._ws_multi is None or self._ws_multi.numel() < need or self._ws_multi.device != dev:
-            self._ws_multi = None
-            self._ws_multi = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        ws = self._ws_multi
-        if jitter is not None:
-            jitter = jitter.to(torch.float32).contiguous()
+        rays_o, rays_d, R, dev = self._rays(rays_o, rays_d)
+        ws = self._scratch("_ws_multi", lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, 1), dev)
+        jitter = self._jitter(jitter)
         live = torch.zeros((), device=dev, dtype=torch.int32)
         hip.check(lib.tgtc_geometry_build(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
                                           R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), min_weight, hip.ptr(ws),
@@ -443,16 +450,24 @@ class RayRenderer:
         lib = hip.load()
         if rays_o.shape[0] != cache.R:
             raise ValueError("build_trunk: %d rays, the cache holds %d" % (rays_o.shape[0], cache.R))
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
+        rays_o, rays_d, _, dev = self._rays(rays_o, rays_d)
         fine = self.fine.packed()
         layout = "fp16x3" if from_mx else fine.precision
-        plane = torch.empty(cache.trunk_nbytes(layout, cache.count), dtype=torch.uint8, device=rays_o.device)
+        plane = torch.empty(cache.trunk_nbytes(layout, cache.count), dtype=torch.uint8, device=dev)
         call = lib.tgtc_geometry_trunk_mx if from_mx else lib.tgtc_geometry_trunk
         hip.check(call(fine.handle, hip.ptr(rays_o), hip.ptr(rays_d), cache.R, cache.n_coarse, cache.n_fine,
                        hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(plane), plane.numel(), hip.stream()))
         cache.attach_trunk(plane, layout, fine.precision)
         return cache
+
+    # (use_trunk, folded, mx) -> the library's restyle.  From the plane the plane consumers, which take no NeRF handle;
+    # otherwise the list kernels behind the fine handle.  The fp16mx forms exist for frame-constant latents only.
+    _RESTYLE = {(False, False, False): "tgtc_restyle_rays",
+                (False, True, False): "tgtc_restyle_rays_folded",
+                (False, True, True): "tgtc_restyle_rays_folded_mx",
+                (True, False, False): "tgtc_restyle_rays_trunk",
+                (True, True, False): "tgtc_restyle_rays_trunk_folded",
+                (True, True, True): "tgtc_restyle_rays_trunk_folded_mx"}
 
     def restyle(self, cache, rays_o, rays_d, zs, key=None, n_coarse=None, n_fine=None, use_trunk=None, style_precision=None):
         """The rays of `cache` under K latent sets: zs float [K,R,32] -> dict rgb [K,R,3], t [R], live (the cache's count, a
@@ -508,40 +523,23 @@ class RayRenderer:
                              % (n_coarse, n_fine, cache.n_coarse, cache.n_fine))
         if key is not None and key != cache.key:
             raise ValueError("restyle: the cache was built under another key")
-        rays_o = rays_o.to(torch.float64).contiguous()
-        rays_d = rays_d.to(torch.float64).contiguous()
-        dev = rays_o.device
-        zs = zs.to(torch.float32).contiguous()
-        folded = zs.dim() == 2
-        if folded:
-            if zs.shape[0] < 1 or zs.shape[1] != 32:
-                raise ValueError("zs must be [K,32] with K >= 1, got %s" % list(zs.shape))
-        elif zs.dim() != 3 or zs.shape[0] < 1 or zs.shape[1] != R or zs.shape[2] != 32:
-            raise ValueError("zs must be [K,%d,32] with K >= 1, got %s" % (R, list(zs.shape)))
-        K = zs.shape[0]
+        rays_o, rays_d, _, dev = self._rays(rays_o, rays_d)
+        zs, K, folded = self._check_zs(zs, R)
         need = (lib.tgtc_restyle_folded_workspace_bytes if folded else lib.tgtc_restyle_workspace_bytes)(cache.count, K)
-        if self._ws_restyle is None or self._ws_restyle.numel() < need or self._ws_restyle.device != dev:
-            self._ws_restyle = None
-            self._ws_restyle = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        ws = self._ws_restyle
+        ws = self._scratch("_ws_restyle", need, dev)
         rgb = torch.empty(K, R, 3, device=dev, dtype=torch.float32)
         t = torch.empty(R, device=dev, dtype=torch.float32)
         if mx:
             self.style.packed().enable_mx()                         # a no-op from the second call on
-            # with a plane the plane consumer; without one the list kernel behind the fp16mx fine handle (no plane is made)
-            call = lib.tgtc_restyle_rays_trunk_folded_mx if use_trunk else lib.tgtc_restyle_rays_folded_mx
-        elif use_trunk:
-            call = lib.tgtc_restyle_rays_trunk_folded if folded else lib.tgtc_restyle_rays_trunk
+        call = getattr(lib, self._RESTYLE[bool(use_trunk), folded, mx])
         if use_trunk:
             hip.check(call(self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R, cache.n_coarse,
                            cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(cache.trunk),
                            cache.trunk.numel(), hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
-            return {"rgb": rgb, "t": t, "live": cache.count}
-        if not mx:
-            call = lib.tgtc_restyle_rays_folded if folded else lib.tgtc_restyle_rays
-        hip.check(call(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K, R,
-                       cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(ws),
-                       ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
+        else:
+            hip.check(call(self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d), hip.ptr(zs), K,
+                           R, cache.n_coarse, cache.n_fine, hip.ptr(cache.buffer), cache.buffer.numel(), cache.count, hip.ptr(ws),
+                           ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.stream()))
         return {"rgb": rgb, "t": t, "live": cache.count}
 
 
