@@ -47,6 +47,19 @@ int tgtc_trainer_overflows(tgtc_trainer* trainer, void* stream, unsigned* count)
  * fine network).  It belongs to ONE forward / backward pair: a second forward before the backward of the first needs its
  * own workspace (the reference's batchify, utils.py:435-456, makes two forwards before one backward). */
 
+/* One training batch of `Origin_train` from shuffled pixel indices (csrc/train_batch.hip), in place of the reference's
+ * float64 ray tables of every pixel of every training frame and the DataLoader's gather of their rows
+ * (dataset.py:63-144).  index[r] = frame * H * W + row * W + col.  Row r of rays_o / rays_d double [R,3] carries the bits
+ * that tgtc_gen_rays writes for that pixel of the camera c2w_table[frame] (float64 get_rays_np + ndc_rays_np, same
+ * intrinsics and flags for every frame); rgb_gt float [R,3] is images[frame, row, col], copied.
+ *   c2w_table  DEVICE float [F,12], 3x4 row-major per frame      images  DEVICE float [F,H,W,3], or NULL with rgb_gt NULL
+ *   index      DEVICE int64 [R]
+ * A row whose index lies outside [0, F*H*W) is not dereferenced: it gets NaN rays and zero colour.  R == 0 is TGTC_OK;
+ * a null index / rays_o / rays_d / c2w_table, rgb_gt without images, or F, H, W <= 0 is TGTC_ERR_ARG. */
+int tgtc_train_batch(int H, int W, double fx, double fy, double cx, double cy, const float* c2w_table, int F,
+                     const float* images, const int64_t* index, int64_t R, int pixel_alignment, int ndc, double ndc_near,
+                     double* rays_o, double* rays_d, float* rgb_gt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,15 @@ def load_nerf(ckpts_path, model, model_fine=None):
     return sd['global_step']
 
 
+def load_nerf_optimizer(ckpts_path):
+    """-> the `optimizer` state dict of the file load_nerf picks (train_tgtcs.py:70), or None without a file.  One Adam
+    over the coarse then the fine parameters, each in nn.Module.parameters() order (train_tgtcs.py:29-39)."""
+    ck = newest(ckpts_path, ['tar'], ['style', 'latent'])
+    if ck is None:
+        return None
+    return torch.load(ck, map_location='cpu').get('optimizer')
+
+
 def load_style(ckpts_path, style_model, concat_model):
     """-> global_step or None (train_tgtcs.py:74-82)."""
     ck = newest(ckpts_path, ['tar', 'style'], ['latent'])

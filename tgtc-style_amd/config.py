@@ -49,10 +49,25 @@ EXTRA = {
     "style_precision": (str, ""),      # --fold_latents with a fine network in fp16mx: "fp16mx" runs the style networks in fp16mx (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
+    "origin_train": (None, False),     # run the reference's Origin_train loop on the HIP training kernels (HELP below)
+    "train_seed": (int, 0),            # --origin_train: seed of the initial weights, the batches and the draws (HELP below)
+    "train_unfused": (None, False),    # --origin_train: train on the per-layer path, the cross-check of the fused kernels
 }
 
 
 HELP = {
+    "origin_train": "train the coarse / fine NeRF pair from the scene (the reference's Origin_train, steps up to "
+                    "--origin_step inclusive): resumes from the newest NNNNNN.tar under the output directory or starts "
+                    "fresh, writes the reference's checkpoint files (every 500 steps and at the end, --ckp_num kept), "
+                    "prints a line every --i_print steps, and returns; the later stages (2-D module, Style_train) stay "
+                    "the reference's.  The scene is --datadir (poses_bounds.npy and images/ or images_<factor>/) or, with "
+                    "--synthetic, a teacher scene rendered from the seeded networks.  Refused together with a --render_* "
+                    "flag and under torchrun (single GPU)",
+    "train_seed": "with --origin_train: seeds the fresh weights, the shuffled batches, the stratified jitter and the "
+                  "density-noise draws; the batch and draws of a step depend on (seed, step) alone, so a resumed run "
+                  "continues the interrupted one.  -1: unseeded, like the reference.  Default 0",
+    "train_unfused": "with --origin_train: differentiable per-layer HIP dense layers in place of the fused training "
+                     "kernels (same arithmetic, one launch per product); the cross-check",
     "synthetic_styles": "styles of the synthetic scene's latent table (default 1)",
     "share_geometry": "with --render_valid_style: render all styles of a frame in one multi-latent call that shares the "
                       "coarse pass, the fine depths and the fine NeRF trunk.  Style 0 is rendered with the jitter it has "

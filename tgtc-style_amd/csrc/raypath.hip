@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "raygen.h"
 #include "raymarch_wave.h"
 
 // The reference evaluates these formulas with separate multiplies and adds (numpy / ATen CPU);
@@ -20,11 +21,8 @@ namespace tgtc {
 // ------------------------------------------------------------------------------------------- rays
 // reference dataset.py:33-42 + dataset.py:44-61
 struct RayGenArgs {
-    int H, W;
-    double fx, fy, cx, cy;
+    RayIntrinsics cam;      // raygen.h: the per-pixel body, shared with train_batch.hip
     float c2w[12];
-    int pixel_alignment, ndc;
-    double ndc_near;
     long long first, n;
 };
 
@@ -32,41 +30,8 @@ __global__ void __launch_bounds__(256) gen_rays_kernel(RayGenArgs a, double* __r
                                                        double* __restrict__ rays_d) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.n) return;
-    const long long pix = a.first + idx;
-    float col = (float)(pix % a.W), row = (float)(pix / a.W);
-    if (a.pixel_alignment) {
-        col = col + 0.5f;
-        row = row + 0.5f;
-    }
-    // dataset.py:37: float32 grid minus float64 intrinsics -> float64
-    const double cam[3] = {((double)col - a.cx) / a.fx, (-((double)row - a.cy)) / a.fy, -1.0};
     double d[3], o[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        // dataset.py:39: sum over the last axis of dirs[...,None,:] * c2w[:3,:3]
-        const double p0 = cam[0] * (double)a.c2w[4 * k + 0];
-        const double p1 = cam[1] * (double)a.c2w[4 * k + 1];
-        const double p2 = cam[2] * (double)a.c2w[4 * k + 2];
-        d[k] = (p0 + p1) + p2;
-        o[k] = (double)a.c2w[4 * k + 3];
-    }
-    if (a.ndc) {
-        // dataset.py:46-47
-        const double t = (-(a.ndc_near + o[2])) / d[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = o[k] + t * d[k];
-        // dataset.py:50-56
-        const double sx = -1.0 / ((double)a.W / (2.0 * a.fx));
-        const double sy = -1.0 / ((double)a.H / (2.0 * a.fx));
-        const double o0 = sx * o[0] / o[2];
-        const double o1 = sy * o[1] / o[2];
-        const double o2 = 1.0 + 2.0 * a.ndc_near / o[2];
-        const double d0 = sx * (d[0] / d[2] - o[0] / o[2]);
-        const double d1 = sy * (d[1] / d[2] - o[1] / o[2]);
-        const double d2 = -2.0 * a.ndc_near / o[2];
-        o[0] = o0, o[1] = o1, o[2] = o2;
-        d[0] = d0, d[1] = d1, d[2] = d2;
-    }
+    pixel_ray(a.cam, a.c2w, a.first + idx, o, d);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         rays_o[idx * 3 + k] = o[k];
@@ -743,9 +708,9 @@ extern "C" int tgtc_gen_rays(int H, int W, double fx, double fy, double cx, doub
     if (n == 0) return TGTC_OK;
     TGTC_REQUIRE(rays_o && rays_d, "gen_rays: null output");
     RayGenArgs a;
-    a.H = H, a.W = W, a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
+    a.cam.H = H, a.cam.W = W, a.cam.fx = fx, a.cam.fy = fy, a.cam.cx = cx, a.cam.cy = cy;
     for (int i = 0; i < 12; ++i) a.c2w[i] = c2w[i];
-    a.pixel_alignment = pixel_alignment, a.ndc = ndc, a.ndc_near = ndc_near, a.first = first_pixel, a.n = n;
+    a.cam.pixel_alignment = pixel_alignment, a.cam.ndc = ndc, a.cam.ndc_near = ndc_near, a.first = first_pixel, a.n = n;
     gen_rays_kernel<<<blocks_for(n, 256), 256, 0, as_stream(stream)>>>(a, rays_o, rays_d);
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;

@@ -1,13 +1,21 @@
 """`python -m tgtc_style_amd.train_tgtcs --config configs/fern.txt --render_valid_style [--synthetic]`
+`python -m tgtc_style_amd.train_tgtcs --config configs/fern.txt --origin_train [--synthetic]`
 
 The render half of the reference entry point (train_tgtcs.py:13-215): build the four networks and the latent
 table, reload the newest checkpoints, and dispatch to render_style / render_train_style (or cal_geometry with
 --render_valid).  Output directory and file names are the reference's (train_tgtcs.py:20,164,196;
-rendering.py:216-217,363-364).  Training loops are out of scope.
+rendering.py:216-217,363-364).
 
-No dataset or checkpoint ships with this repository (and the LLFF loader is a `next` row of SURVEY section 8f), so
-`--synthetic` provides a seeded scene: synth.nerf_state/... weights and a closed-form camera path.  Without it
-the reference layout is expected: <sv_path>/NNNNNN.tar, style_NNNNNN.tar, latent_NNNNNN.tar.
+Of the training half, `--origin_train` runs the reference's first stage, `Origin_train` (train_tgtcs.py:218-309), on the
+HIP training kernels: the NeRF pair is trained from the scene's images up to --origin_step, resuming from the newest
+NNNNNN.tar or starting fresh, and leaves the reference's checkpoint files (train_loop.py, train_data.py).  A mode the
+caller asks for: without the flag nothing trains.  The later stages (the 2-D module's training, `Style_train` and its VGG
+losses) are the reference's and stay out of this build.
+
+No dataset or checkpoint ships with this repository, so `--synthetic` provides a seeded scene: synth.nerf_state/...
+weights and a closed-form camera path (for --origin_train: a teacher scene rendered from those weights, and seeded
+student weights).  Without it the reference layout is expected: <sv_path>/NNNNNN.tar, style_NNNNNN.tar,
+latent_NNNNNN.tar to render from, <datadir>/poses_bounds.npy and images/ or images_<factor>/ to train from.
 """
 import os
 import sys
@@ -172,6 +180,46 @@ def _broadcast_from_rank0(t, dist):
         t.copy_(host)
 
 
+def _origin_train(args, device, sv_path, model, model_fine, concat_model, style_model):
+    """--origin_train: the first stage of the reference's schedule (train_tgtcs.py:56-72,108-113,563-571) -> sv_path."""
+    from . import train_data, train_loop
+    if not args.synthetic:
+        missing = train_data.missing_scene_parts(args.datadir, args.factor)
+        if missing:
+            raise SystemExit("train_tgtcs: --origin_train needs a scene to train from: --datadir %s has no %s (or run with "
+                             "--synthetic for the seeded teacher scene)" % (args.datadir, " and no ".join(missing)))
+    global_step, first_step, optimizer_state = 0, 0, None
+    step = None if args.no_reload else checkpoints.load_nerf(sv_path, model, model_fine)           # train_tgtcs.py:60-72
+    if step is not None:
+        # The file holds the state AFTER iteration `step`.  The reference re-runs that iteration on reload (one extra Adam
+        # step); here the run continues with the next one, as the uninterrupted run would.
+        global_step, first_step = int(step), int(step) + 1
+        optimizer_state = checkpoints.load_nerf_optimizer(sv_path)
+    elif args.synthetic:
+        model.load_state_dict(_t(synth.nerf_state(10)))             # seeded, well-conditioned students (teacher: 0 / 1)
+        model_fine.load_state_dict(_t(synth.nerf_state(11)))
+    if global_step + 1 >= args.origin_step:                          # train_tgtcs.py:109
+        print('Origin_train: global step %d has reached --origin_step %d, nothing to train' % (global_step, args.origin_step))
+        return sv_path
+    if step is not None:
+        print('Resuming Origin_train from the checkpoint of step %d in %s: continuing at step %d' % (global_step, sv_path, first_step))
+    else:
+        print('Origin_train: no NeRF checkpoint in %s, starting at step 0 from %s' % (
+            sv_path, 'the seeded synthetic students' if args.synthetic else 'freshly initialised networks'))
+    if args.synthetic:
+        data = train_data.TrainRays.from_synthetic(args, device)
+    else:
+        data = train_data.TrainRays.from_llff(args.datadir, args.factor, device, no_ndc=args.no_ndc,
+                                              pixel_alignment=args.pixel_alignment)
+    print('Origin_train: %d frames of %d x %d, %d rays, %d per batch' % (data.frame_num, data.h, data.w, data.rays_num,
+                                                                         args.batch_size))
+    end = train_loop.origin_train(args, model, model_fine, data, sv_path, first_step, optimizer_state=optimizer_state,
+                                  style_optimizer=train_loop.make_style_optimizer(args, style_model, concat_model))
+    print('Origin_train done at step %d, checkpoints in %s.  The later stages (the 2-D module, Style_train) are the '
+          "reference's" % (end - 1, sv_path))
+    return sv_path
+
+
 def train(args):
     rank, world, local, dist = _init_distributed()
     if not torch.cuda.is_available():
@@ -183,10 +231,14 @@ def train(args):
                            'ImgFactor' + str(int(args.factor)))        # train_tgtcs.py:19-20
     os.makedirs(sv_path, exist_ok=True)
 
+    if args.origin_train and args.train_seed >= 0:
+        torch.manual_seed(args.train_seed)      # a fresh start trains the default nn.Linear initialisation, as the reference
     model = models.StyleNerf(args, mode='coarse').to(device)
     model_fine = models.StyleNerf(args, mode='fine').to(device)
     concat_model = models.StyleMLP_before_concat(args).to(device)
     style_model = models.StyleMLP_Wild_multilayers(args).to(device)
+    if args.origin_train:
+        return _origin_train(args, device, sv_path, model, model_fine, concat_model, style_model)
     global_step = 0
     step = None if args.no_reload else checkpoints.load_nerf(sv_path, model, model_fine)           # train_tgtcs.py:60-72
     nerf_step = -1 if step is None else int(step)      # part of the --geometry_cache keys (-1: the seeded synthetic weights)
@@ -290,8 +342,9 @@ def train(args):
                                    renderer=rendering.RayRenderer(model, model_fine), **common)
             print('Done, saving to', out)
             return out
-    raise SystemExit("train_tgtcs: nothing to do -- pass --render_valid_style, --render_train_style or --render_valid "
-                     "(the training loops of the reference are outside this build)")
+    raise SystemExit("train_tgtcs: nothing to do -- pass --render_valid_style, --render_train_style, --render_valid or "
+                     "--origin_train (of the reference's training stages only Origin_train is part of this build, and only "
+                     "when asked for)")
 
 
 def _finish_distributed():
@@ -326,6 +379,14 @@ def main(argv=None):
             raise SystemExit("train_tgtcs: --style_precision fp16mx needs a --precision whose fine half is fp16mx, e.g. "
                              "fp16x3+fp16mx (got %s; the kernel runs the fine trunk and the style networks of a tile together)"
                              % args.precision)
+    if args.origin_train:
+        renders = [f for f in ("render_valid", "render_train", "render_valid_style", "render_train_style") if getattr(args, f)]
+        if renders:
+            raise SystemExit("train_tgtcs: --origin_train trains and returns; it does not go with --%s (render from the "
+                             "checkpoints in a second call)" % " / --".join(renders))
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("train_tgtcs: --origin_train runs on one GPU (WORLD_SIZE = %s): the reference has no "
+                             "data-parallel training and neither has this build" % os.environ["WORLD_SIZE"])
     if args.expname is None:
         raise SystemExit("train_tgtcs: --expname (or --config) is required")
     try:

@@ -4,9 +4,10 @@ sampling with jitter, coarse NeRF, compositing with the density-noise regularise
 
 The networks must be marked `.trainable()` (models.StyleNerf): their forward then runs layer by layer on the differentiable
 HIP dense layers (autograd_ops.py) and `utils.alpha_composition` carries its own backward kernel.  The samplers carry no
-gradient, as in the reference (utils.py:562-579 detach).  The loops around this body -- data loading, learning-rate decay,
-checkpoint cadence (checkpoints.py writes the files), the style stages -- are the reference's own training driver and stay
-outside this build."""
+gradient, as in the reference (utils.py:562-579 detach).  The loop around `origin_train_step` -- shuffled batches, learning-rate decay,
+checkpoint cadence, logging -- is train_loop.origin_train (`train_tgtcs --origin_train`); the loop around
+`style_train_step` and the style stages' VGG losses are the reference's own training driver and stay outside this build
+(SURVEY section 8f rank 4)."""
 import torch
 
 from . import utils
@@ -17,23 +18,31 @@ def img2mse(x, y):
 
 
 def origin_train_step(model, model_fine, optimizer, rays_o, rays_d, rgb_gt, N_samples, N_samples_fine, near, far,
-                      sigma_noise_std=1.0, jitter=None, as_float=True):
+                      sigma_noise_std=1.0, jitter=None, as_float=True, generator=None):
     """-> dict(loss, loss_rgb, loss_rgb_fine); parameters of both networks updated in place.  as_float=False returns the
     losses as detached device scalars WITHOUT synchronising: the reference reads them only every i_print iterations
-    (train_tgtcs.py:257-266), and a float() per iteration serialises the host with the GPU."""
+    (train_tgtcs.py:257-266), and a float() per iteration serialises the host with the GPU.  generator (a device
+    torch.Generator): the stratified jitter (unless `jitter` is given) and the two density-noise planes are drawn from it,
+    in that order, instead of from the global generator -- a seeded iteration."""
     val = (lambda t: float(t.detach())) if as_float else (lambda t: t.detach())
     R = rays_o.shape[0]
+    noise = lambda n: None
+    if generator is not None:
+        if jitter is None:
+            jitter = torch.rand(R, N_samples, device=rays_o.device, generator=generator)
+        if sigma_noise_std > 0:
+            noise = lambda n: torch.randn(R, n, device=rays_o.device, generator=generator) * sigma_noise_std
     pts, ts = utils.sampling_pts_uniform(rays_o=rays_o, rays_d=rays_d, N_samples=N_samples, near=near, far=far, perturb=True,
                                          jitter=jitter)
     ret = model(pts=pts, dirs=rays_d.unsqueeze(1).expand([R, N_samples, 3]))
-    rgb_exp, _, weights = utils.alpha_composition(ret['rgb'], ret['sigma'], ts, sigma_noise_std)
+    rgb_exp, _, weights = utils.alpha_composition(ret['rgb'], ret['sigma'], ts, sigma_noise_std, noise=noise(N_samples))
     loss_rgb = img2mse(rgb_gt, rgb_exp)
     loss, out = loss_rgb, {}
     if N_samples_fine > 0:
         pts_fine, ts_fine = utils.sampling_pts_fine_torch(rays_o, rays_d, ts, weights.detach(), N_samples_fine)
         n = N_samples + N_samples_fine
         ret = model_fine(pts=pts_fine, dirs=rays_d.unsqueeze(1).expand([R, n, 3]))
-        rgb_exp_fine, _, _ = utils.alpha_composition(ret['rgb'], ret['sigma'], ts_fine, sigma_noise_std)
+        rgb_exp_fine, _, _ = utils.alpha_composition(ret['rgb'], ret['sigma'], ts_fine, sigma_noise_std, noise=noise(n))
         loss_rgb_fine = img2mse(rgb_gt, rgb_exp_fine)
         loss = loss + loss_rgb_fine
         out['loss_rgb_fine'] = val(loss_rgb_fine)
