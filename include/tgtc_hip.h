@@ -256,12 +256,16 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
 
 /* ------------------------------------------------------------------ a8: latent table
  * models.py:490-506 StyleLatents_variational.forward.  latents float [S,F,D] device, mu float [S,D] device,
- * style_ids / frame_ids int64 [R] device.  tile7: the llff `repeat((7,1))` wrap (models.py:496). */
+ * style_ids / frame_ids int64 [R] device.  tile7: the llff `repeat((7,1))` wrap (models.py:496).
+ * The ids live on the device and are NOT checked here: every style id must lie in [0, S), every frame id must be >= 0 and
+ * style * F + frame must be < S * F (< 7 * S * F with tile7).  The kernels index mu[style] and the flattened table with them,
+ * so anything else reads -- and tgtc_latents_backward's atomics write -- out of bounds.  They are the caller's
+ * responsibility (the Python binding raises IndexError on the host before it launches: models.check_latent_ids). */
 int tgtc_latents_forward(const float* latents, const float* mu, int S, int F, int D, const int64_t* style_ids,
                          const int64_t* frame_ids, int64_t R, float sigma_scale, int tile7, float* out, void* stream);
 /* Its gradient for the training side (Style_train optimises the table, train_tgtcs.py:312-571): grad_out [R,D] ->
  * d_latents [S,F,D] += sigma_scale * g at the gathered rows, d_mu [S,D] += (1 - sigma_scale) * g; both buffers zeroed by the
- * caller, either may be NULL. */
+ * caller, either may be NULL.  The same rule for the ids: unchecked here, the caller's responsibility. */
 int tgtc_latents_backward(const float* grad_out, int S, int F, int D, const int64_t* style_ids, const int64_t* frame_ids,
                           int64_t R, float sigma_scale, int tile7, float* d_latents, float* d_mu, void* stream);
 

@@ -108,7 +108,9 @@ int tgtc_s2d_linear_pre(const float* x, int64_t M, int K, const float* W, const 
  *   dW[N,K] = dy^T . x,  db[N] = column sums of dy   (NULL to skip either)
  * as GEMMs on the same kernel: dy and x are transposed into the workspace, the sample dimension is split over GEMM batches
  * and the partial products summed.  relu_y (NULL, or the forward's output [M,N] when it fused a ReLU) gates dy on the fly:
- * elements with relu_y <= 0 carry no gradient. */
+ * elements with relu_y <= 0 carry no gradient.  The gradients enter the fp16 operands rescaled by powers of two that never
+ * leave the device: one per sample row for dx (rows of very different size keep their precision), one per call for dW and db
+ * (which sum over the samples). */
 size_t tgtc_s2d_linear_backward_workspace_bytes(int64_t M, int K, int N);
 int tgtc_s2d_linear_backward(const float* x, const float* dy, const float* relu_y, const float* W, int64_t M, int K, int N,
                              int precision, void* workspace, size_t workspace_bytes, float* dx, float* dW, float* db,

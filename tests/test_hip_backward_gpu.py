@@ -171,22 +171,7 @@ def test_fused_training_path_matches_the_unfused_one():
             assert float(db.abs().max()) <= 3e-5 * sb, (M, l, "bias", float(db.abs().max()) / sb, S[:10].tolist())
 
 
-def _float64_preactivations(sd, pts, dirs):
-    """every ReLU layer's pre-activations of the oracle's network in float64: [M, units] (models.py:95-111)"""
-    w = {k: v.double() for k, v in T(sd).items()}
-    pe, de = fields.posenc(pts, 10).double(), fields.posenc(dirs, 4).double()
-    lin = lambda name, x: x @ w["net.%s.weight" % name].T + w["net.%s.bias" % name]
-    zs, h = [], None
-    for i in range(8):
-        x = pe if i == 0 else (torch.cat([pe, h], -1) if i == 5 else h)
-        z = lin("base_layers.%d" % i, x)
-        zs.append(z)
-        h = torch.relu(z)
-    z = lin("base_remap_layer", h)
-    zs.append(z)
-    z = lin("rgb_layers.0", torch.cat([torch.relu(z), de], -1))
-    zs.append(z)
-    return torch.cat(zs, -1)
+from train_kernel_cases import float64_preactivations as _float64_preactivations      # (state dict, pts, dirs) -> [M, units]
 
 
 def test_fused_and_unfused_gradients_agree_element_wise_away_from_relu_kinks():

@@ -10,13 +10,7 @@ from oracle import raymarch
 pytestmark = pytest.mark.gpu
 
 
-def _inputs(R, N, seed):
-    rng = np.random.default_rng(seed)
-    rgb = torch.from_numpy(rng.random((R, N, 3)).astype(np.float32))
-    sigma = torch.from_numpy((rng.standard_normal((R, N)) * 8).astype(np.float32))
-    ts = torch.from_numpy(np.sort(rng.random((R, N)).astype(np.float32), -1))
-    noise = torch.from_numpy(rng.standard_normal((R, N)).astype(np.float32))
-    return rgb, sigma, ts, noise
+from train_kernel_cases import base_inputs as _inputs          # (R, N, seed) -> rgb, sigma, sorted depths, noise
 
 
 @pytest.mark.parametrize("N", [7, 64, 128, 192])

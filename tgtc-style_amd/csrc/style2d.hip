@@ -127,6 +127,7 @@ struct GemmOut {
     int relu;
     long long bias_batch_stride = 0; // floats between the bias vectors of consecutive batches (blockIdx.z)
     const float* alpha_dev = nullptr; // optional second scale factor read from device memory (gradient rescaling)
+    const float* row_alpha = nullptr; // optional third one per output row m, [M] in device memory (per-sample gradient rescaling)
 };
 
 // four fp32 values -> fp16 hi (+ lo) halves in LDS.  The lo halves come straight out of v_fma_mixlo/mixhi_f16
@@ -293,7 +294,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(AL al, DenseRows bl, GemmOut 
                 const int m = m0 + 16 * WT * wm + 16 * i + 4 * g + r;
                 if (m >= M) continue;
                 const long long o = (long long)m * out.sm + (long long)n * out.sn;
-                float v = alpha * acc[i][j][r] + b;
+                const float am = out.row_alpha ? alpha * out.row_alpha[m] : alpha;
+                float v = am * acc[i][j][r] + b;
                 if (out.res) v += out.res[o];
                 if (out.relu) v = fmaxf(v, 0.0f);
                 out.C[o] = v;
@@ -634,13 +636,14 @@ __global__ void __launch_bounds__(256) transpose_ld_kernel(const float* __restri
     for (int j = ty; j < 32; j += 8)
         if (bx + j < cols && by + tx < rows) out[(long long)(bx + j) * ld_out + by + tx] = tile[tx][j] * (scale ? *scale : 1.0f);
 }
-// out halves = split(gate ? in * scale : 0): the scaled, ReLU-gated gradient as a pre-split GEMM operand
-__global__ void __launch_bounds__(256) scale_split_kernel(const float* __restrict__ in, long long n, const float* __restrict__ sc,
-                                                          const float* __restrict__ gate, half_t* __restrict__ hi,
-                                                          half_t* __restrict__ lo) {
+// out halves = split(gate ? in * scale : 0): the scaled, ReLU-gated gradient as a pre-split GEMM operand; the scale is the
+// one of the element's row (row_inv [rows]: its reciprocal, a power of two), cols elements per row
+__global__ void __launch_bounds__(256) scale_split_kernel(const float* __restrict__ in, long long n, int cols,
+                                                          const float* __restrict__ row_inv, const float* __restrict__ gate,
+                                                          half_t* __restrict__ hi, half_t* __restrict__ lo) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float v = (gate && !(gate[i] > 0.0f)) ? 0.0f : in[i] * sc[1];
+    const float v = (gate && !(gate[i] > 0.0f)) ? 0.0f : in[i] * (1.0f / row_inv[i / cols]);
     const half_t h = (half_t)v;
     hi[i] = h, lo[i] = (half_t)(v - (float)h);
 }
@@ -696,10 +699,30 @@ __global__ void grad_scale_kernel(float* __restrict__ sc) {
     const int k = ok ? max(-100, min(100, 10 - e)) : 0;
     sc[1] = ldexpf(1.0f, k), sc[2] = ldexpf(1.0f, -k);
 }
-__global__ void __launch_bounds__(256) scale_copy_kernel(const float* __restrict__ in, long long n, const float* __restrict__ sc,
-                                                         float* __restrict__ out, const float* __restrict__ gate) {
+__global__ void __launch_bounds__(256) scale_copy_kernel(const float* __restrict__ in, long long n, int cols,
+                                                         const float* __restrict__ row_inv, float* __restrict__ out,
+                                                         const float* __restrict__ gate) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (gate && !(gate[i] > 0.0f)) ? 0.0f : in[i] * sc[1];
+    if (i < n) out[i] = (gate && !(gate[i] > 0.0f)) ? 0.0f : in[i] * (1.0f / row_inv[i / cols]);
+}
+// The scale of ONE sample's gradient row for dx = dy . W: a batch mixes rows of very different size (a sample behind a
+// surface carries 2^-30 of its neighbour's gradient), and under one scale for the whole batch the small rows fall below the
+// fp16 range of the split and come out with a few bits.  dx's rows do not mix samples, so each gets its own power of two --
+// largest magnitude of the row (ungated, as absmax_kernel) to ~2^10 -- and the GEMM epilogue scales row m back by
+// row_inv[m] = 2^-k.  |k| <= 126 keeps both factors normal floats; a zero / non-finite row keeps k = 0.  One wave per row.
+__global__ void __launch_bounds__(256) row_scale_kernel(const float* __restrict__ g, long long rows, int cols,
+                                                        float* __restrict__ row_inv) {
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;   // wave-uniform
+    unsigned m = 0;
+    for (int c = threadIdx.x & 63; c < cols; c += 64) m = max(m, __float_as_uint(fabsf(g[r * cols + c])));
+#pragma unroll
+    for (int off = 32; off; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+    if ((threadIdx.x & 63) == 0) {
+        const int e = (int)((m >> 23) & 0xff) - 127;
+        const bool ok = m != 0 && ((m >> 23) & 0xff) != 0xff;
+        row_inv[r] = ldexpf(1.0f, ok ? -max(-126, min(126, 10 - e)) : 0);
+    }
 }
 // out[i] = sum_s part[s][i]
 __global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ part, int nsplit, long long n,
@@ -1426,7 +1449,7 @@ extern "C" size_t tgtc_s2d_linear_backward_workspace_bytes(int64_t M, int K, int
     int64_t mc;
     backward_split(M, K, N, nsplit, mc);
     const size_t mpad = (size_t)nsplit * mc;
-    return ((size_t)N * mpad + (size_t)K * mpad + (size_t)nsplit * N * K + (size_t)K * N + (size_t)M * N + 8 * 64) * sizeof(float);
+    return ((size_t)N * mpad + (size_t)K * mpad + (size_t)nsplit * N * K + (size_t)K * N + (size_t)M * N + (size_t)M + 8 * 64) * sizeof(float);
 }
 
 extern "C" int tgtc_s2d_linear_backward(const float* x, const float* dy, const float* relu_y, const float* W, int64_t M, int K,
@@ -1450,19 +1473,22 @@ extern "C" int tgtc_s2d_linear_backward(const float* x, const float* dy, const f
     float* xT = ws.take((size_t)K * mpad);
     float* part = ws.take((size_t)nsplit * N * K);
     float* WT = ws.take((size_t)K * N);
-    float* dys = ws.take((size_t)mn);              // s * dy
+    float* dys = ws.take((size_t)mn);              // s_m * dy, row m at its own scale (dx only)
+    float* row_inv = ws.take((size_t)M);           // 1 / s_m
     if (!ws.ok) return fail(TGTC_ERR_ARG, "s2d_linear_backward: workspace too small");
     TGTC_HIP_CHECK(hipMemsetAsync(sc, 0, 16, st));
     absmax_kernel<<<(unsigned)std::min<long long>(1024, (mn + 255) / 256), 256, 0, st>>>(dy, mn, reinterpret_cast<unsigned*>(sc), nullptr);   // ungated maximum >= gated one: as good a scale, half the bytes
     TGTC_LAUNCH_CHECK();
     grad_scale_kernel<<<1, 1, 0, st>>>(sc);
     TGTC_LAUNCH_CHECK();
-    if (dx) {   // dx[M,K] = dy[M,N] . W[N,K]: a linear layer on s*dy whose weight is W^T [K,N], scaled back by 1/s
-        half_t* dyh = reinterpret_cast<half_t*>(dys);      // s * gated dy as halves: [M,N] hi, then lo
+    if (dx) {   // dx[M,K] = dy[M,N] . W[N,K]: a linear layer on s_m*dy whose weight is W^T [K,N], row m scaled back by 1/s_m
+        half_t* dyh = reinterpret_cast<half_t*>(dys);      // s_m * gated dy as halves: [M,N] hi, then lo
         half_t* dyl = dyh + (size_t)mn;
         const bool a_pre = N % 4 == 0;
-        if (a_pre) scale_split_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, sc, relu_y, dyh, dyl);
-        else scale_copy_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, sc, dys, relu_y);
+        row_scale_kernel<<<(unsigned)((M + 3) / 4), 256, 0, st>>>(dy, M, N, row_inv);
+        TGTC_LAUNCH_CHECK();
+        if (a_pre) scale_split_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, N, row_inv, relu_y, dyh, dyl);
+        else scale_copy_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, N, row_inv, dys, relu_y);
         TGTC_LAUNCH_CHECK();
         const dim3 g((K + 31) / 32, (N + 31) / 32);
         transpose_ld_kernel<<<g, 256, 0, st>>>(W, N, K, WT, N);
@@ -1476,7 +1502,7 @@ extern "C" int tgtc_s2d_linear_backward(const float* x, const float* dy, const f
             bl.h16 = w16, bl.l16 = w16 + (size_t)K * N;
         }
         GemmOut out{dx, K, 1, 0, nullptr, nullptr, 1.0f, 0};
-        out.alpha_dev = sc + 2;
+        out.row_alpha = row_inv;
         TGTC_TRY((launch_gemm<DenseRows, false>(&h, al, bl, out, (int)M, K, N, 1, st)));
     }
     half_t* dth = reinterpret_cast<half_t*>(dyT);      // (s * gated dy)^T as halves [N, mpad] each, zero padded

@@ -422,8 +422,26 @@ class _LatentGather(torch.autograd.Function):
         return d_lat, d_mu, None, None, None, None
 
 
+def check_latent_ids(style_ids, frame_ids, style_num, frame_num, tile7):
+    """The ids tgtc_latents_forward / _backward accept (the kernels index mu[sid], d_mu[sid] and the flattened table and
+    check nothing: ids are the caller's responsibility at the C level).  IndexError unless every style id lies in
+    [0, style_num), every frame id is >= 0 and flat = sid * frame_num + fid lies inside the table (tiled x7 for llff).  Runs
+    on whatever device the ids live on and launches nothing of this library.  The reference indexes style_latents_mu[style_ids]
+    the Python way, so a negative style id wraps there; here it is refused."""
+    if not style_ids.numel():
+        return
+    rows = style_num * frame_num
+    limit = 7 * rows if tile7 else rows
+    bad = (style_ids < 0) | (style_ids >= style_num) | (frame_ids < 0) | (style_ids * frame_num + frame_ids >= limit)
+    if bool(bad.any()):          # one read-back for the whole rule
+        i = int(torch.nonzero(bad.reshape(-1))[0])
+        raise IndexError("latent index out of range: style id %d, frame id %d (%d styles x %d frames%s)" % (
+            int(style_ids.reshape(-1)[i]), int(frame_ids.reshape(-1)[i]), style_num, frame_num, ", tiled x7" if tile7 else ""))
+
+
 class StyleLatents_variational(nn.Module):
-    """reference models.py:475-506, :535-539."""
+    """reference models.py:475-506, :535-539.  forward() raises IndexError for ids outside the tables (check_latent_ids)
+    before any kernel is launched."""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -450,11 +468,7 @@ class StyleLatents_variational(nn.Module):
         sid = style_ids.to(device=dev, dtype=torch.int64).contiguous()
         fid = frame_ids.to(device=dev, dtype=torch.int64).contiguous()
         tile7 = kwargs.get('type', 'llff') == 'llff'
-        rows = self.style_num * self.frame_num
-        flat = sid * self.frame_num + fid
-        limit = 7 * rows if tile7 else rows
-        if flat.numel() and (int(flat.max()) >= limit or int(flat.min()) < 0):
-            raise IndexError("latent index out of range (%d rows%s)" % (rows, ", tiled x7" if tile7 else ""))
+        check_latent_ids(sid, fid, self.style_num, self.frame_num, tile7)
         if torch.is_grad_enabled() and (self.latents.requires_grad or self.style_latents_mu.requires_grad) and self.differentiable:
             return _LatentGather.apply(self.latents, self.style_latents_mu, sid, fid, float(self.sigma_scale), bool(tile7))
         out = torch.empty(sid.shape[0], self.latent_dim, device=dev, dtype=torch.float32)
