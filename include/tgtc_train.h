@@ -60,6 +60,27 @@ int tgtc_train_batch(int H, int W, double fx, double fy, double cx, double cy, c
                      const float* images, const int64_t* index, int64_t R, int pixel_alignment, int ndc, double ndc_near,
                      double* rays_o, double* rays_d, float* rgb_gt, void* stream);
 
+/* Both batches of one `Style_train` iteration in one launch (csrc/style_train_batch.hip), in place of the reference's
+ * StyleRaySampler_gen / LightDataLoader, which build them row by row on the host (dataset.py:498-539, :658-779).  Every
+ * output has R + n_coh rows.
+ *   rows 0 .. R-1      decode index[r] = style * F*H*W + frame * H*W + row * W + col (dataset.py:498-502)
+ *   rows R .. R+n_coh-1  the frame-ordered batch of loss_coh_get_batch: pixel (coh_start + i) mod (H*W) of frame coh_frame
+ *                      of style coh_style; no index is read for them
+ * rays_o / rays_d double [.,3]: the bits tgtc_gen_rays writes for that pixel of camera c2w_table[frame]; rgb_gt float [.,3]
+ * = float(stylized[style, frame, row, col]) / 255, a float32 division; rgb_origin float [.,3] = images[frame, row, col],
+ * copied; style_id / frame_id int64 [.].  rgb_gt, rgb_origin, style_id, frame_id may each be NULL.
+ *   c2w_table  DEVICE float [F,12]          images    DEVICE float [F,H,W,3], or NULL with rgb_origin NULL
+ *   index      DEVICE int64 [R], or NULL with R == 0      stylized  DEVICE uint8 [S,F,H,W,3], or NULL with rgb_gt NULL
+ * A row whose index lies outside [0, S*F*H*W) is not dereferenced: NaN rays, zero colours, ids -1.  R == 0 && n_coh == 0
+ * is TGTC_OK with nothing written.  TGTC_ERR_ARG, nothing launched: H, W, F or S <= 0; a null c2w_table, rays_o or rays_d;
+ * a null index with R > 0; a colour output without its table; with n_coh > 0, coh_style outside [0,S), coh_frame outside
+ * [0,F) or coh_start < 0. */
+int tgtc_style_train_batch(int H, int W, double fx, double fy, double cx, double cy, const float* c2w_table, int F, int S,
+                           const float* images, const uint8_t* stylized, const int64_t* index, int64_t R, int64_t n_coh,
+                           int coh_style, int coh_frame, int64_t coh_start, int pixel_alignment, int ndc, double ndc_near,
+                           double* rays_o, double* rays_d, float* rgb_gt, float* rgb_origin, int64_t* style_id,
+                           int64_t* frame_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

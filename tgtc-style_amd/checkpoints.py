@@ -99,6 +99,15 @@ def load_style(ckpts_path, style_model, concat_model):
     return sd['global_step']
 
 
+def load_style_optimizer(ckpts_path):
+    """-> the `optimizer` state dict of the file load_style picks, or None without a file.  One Adam over the style MLP's
+    then the concat MLP's parameters (train_tgtcs.py:54)."""
+    ck = newest(ckpts_path, ['tar', 'style'], ['latent'])
+    if ck is None:
+        return None
+    return torch.load(ck, map_location='cpu').get('optimizer')
+
+
 def load_latents(ckpts_path, latents_model):
     """-> True if a latent checkpoint was found (train_tgtcs.py:139-146)."""
     ck = newest(ckpts_path, ['tar', 'latent'], ['style'])

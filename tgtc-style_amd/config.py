@@ -52,6 +52,9 @@ EXTRA = {
     "origin_train": (None, False),     # run the reference's Origin_train loop on the HIP training kernels (HELP below)
     "train_seed": (int, 0),            # --origin_train: seed of the initial weights, the batches and the draws (HELP below)
     "train_unfused": (None, False),    # --origin_train: train on the per-layer path, the cross-check of the fused kernels
+    "style_train": (None, False),      # run the reference's Style_train loop: style MLPs and latent table (HELP below)
+    "coh_until": (int, 122000),        # --style_train: last step with the coherence term in the style optimiser's loss
+    "latent_lrate": (float, 1e-3),     # --style_train: learning rate of the latent table's own Adam
 }
 
 
@@ -63,11 +66,24 @@ HELP = {
                     "the reference's.  The scene is --datadir (poses_bounds.npy and images/ or images_<factor>/) or, with "
                     "--synthetic, a teacher scene rendered from the seeded networks.  Refused together with a --render_* "
                     "flag and under torchrun (single GPU)",
-    "train_seed": "with --origin_train: seeds the fresh weights, the shuffled batches, the stratified jitter and the "
+    "train_seed": "with --origin_train / --style_train: seeds the fresh weights, the shuffled batches, the stratified jitter and the "
                   "density-noise draws; the batch and draws of a step depend on (seed, step) alone, so a resumed run "
                   "continues the interrupted one.  -1: unseeded, like the reference.  Default 0",
     "train_unfused": "with --origin_train: differentiable per-layer HIP dense layers in place of the fused training "
                      "kernels (same arithmetic, one launch per product); the cross-check",
+    "style_train": "train the two style MLPs and the latent table on the frozen NeRF pair (the reference's Style_train, "
+                   "steps up to --total_step inclusive).  NeRF weights from the newest NNNNNN.tar, style MLPs from the "
+                   "newest style_*.tar or freshly initialised, latents from the newest latent_*.tar, else the VAE, else "
+                   "(--synthetic) the seeded table.  Starts after the newest style checkpoint, else after the NeRF "
+                   "checkpoint (refused while that is short of --origin_step), else at 0.  Data: --datadir "
+                   "(poses_bounds.npy, stylized_gen_<factor>/stylized_data.npz and NNN.jpg) and the rgb_*.png of "
+                   "--render_train under the output directory, or with --synthetic the teacher frames and "
+                   "--synthetic_styles recoloured copies.  --batch_size_style rows per batch, constant --lrate, writes "
+                   "style_NNNNNN.tar / latent_NNNNNN.tar on the reference's cadence (--i_weights, --ckp_num), prints a "
+                   "line every --i_print steps.  Refused together with --origin_train, a --render_* flag and under torchrun",
+    "coh_until": "with --style_train: the coherence term is part of the style optimiser's loss while step <= this "
+                 "(default 122000, the reference's literal)",
+    "latent_lrate": "with --style_train: learning rate of the latent table's own Adam (default 1e-3, the reference's literal)",
     "synthetic_styles": "styles of the synthetic scene's latent table (default 1)",
     "share_geometry": "with --render_valid_style: render all styles of a frame in one multi-latent call that shares the "
                       "coarse pass, the fine depths and the fine NeRF trunk.  Style 0 is rendered with the jitter it has "

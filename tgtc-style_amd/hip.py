@@ -46,6 +46,9 @@ _SIGNATURES = {
                       c_int64, c_int64, c_void_p, c_void_p, c_void_p],
     "tgtc_train_batch": [c_int, c_int, c_double, c_double, c_double, c_double, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                          c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p],      # include/tgtc_train.h
+    "tgtc_style_train_batch": [c_int, c_int, c_double, c_double, c_double, c_double, c_void_p, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_int, c_double,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_sample_coarse": [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_posenc": [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p],
     "tgtc_nerf_create": [ctypes.POINTER(Linear), c_int, c_int, ctypes.POINTER(c_void_p)],

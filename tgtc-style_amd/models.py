@@ -441,7 +441,8 @@ def check_latent_ids(style_ids, frame_ids, style_num, frame_num, tile7):
 
 class StyleLatents_variational(nn.Module):
     """reference models.py:475-506, :535-539.  forward() raises IndexError for ids outside the tables (check_latent_ids)
-    before any kernel is launched."""
+    before any kernel is launched.  The check reads one boolean back from the device; `check_ids=False` (forward and
+    minus_logp) skips it for ids the caller guarantees, so that a training loop does not wait for the GPU every step."""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -468,7 +469,8 @@ class StyleLatents_variational(nn.Module):
         sid = style_ids.to(device=dev, dtype=torch.int64).contiguous()
         fid = frame_ids.to(device=dev, dtype=torch.int64).contiguous()
         tile7 = kwargs.get('type', 'llff') == 'llff'
-        check_latent_ids(sid, fid, self.style_num, self.frame_num, tile7)
+        if kwargs.get('check_ids', True):       # False: ids known to be in range (a kernel's, an in-range sampler's): no read-back
+            check_latent_ids(sid, fid, self.style_num, self.frame_num, tile7)
         if torch.is_grad_enabled() and (self.latents.requires_grad or self.style_latents_mu.requires_grad) and self.differentiable:
             return _LatentGather.apply(self.latents, self.style_latents_mu, sid, fid, float(self.sigma_scale), bool(tile7))
         out = torch.empty(sid.shape[0], self.latent_dim, device=dev, dtype=torch.float32)
@@ -482,7 +484,7 @@ class StyleLatents_variational(nn.Module):
         """models.py:526-533: sum((z - mu)^2 / (exp(0.5 logvar) + 1e-3)) over the latent, mean over the rays (mu and logvar
         detached).  Loss-side arithmetic on [R,32] tensors, as in the reference."""
         style_ids, frame_ids = kwargs['style_ids'], kwargs['frame_ids']
-        z = self(style_ids=style_ids, frame_ids=frame_ids, type=kwargs['data_type'])
+        z = self(style_ids=style_ids, frame_ids=frame_ids, type=kwargs['data_type'], check_ids=kwargs.get('check_ids', True))
         sid = style_ids.to(z.device).long()
         mu, logvar = self.style_latents_mu.detach()[sid], self.style_latents_logvar.detach()[sid]
         return torch.sum((z - mu) ** 2 / (torch.exp(0.5 * logvar) + 1e-3), -1).mean()

@@ -1,5 +1,6 @@
 """`python -m tgtc_style_amd.train_tgtcs --config configs/fern.txt --render_valid_style [--synthetic]`
 `python -m tgtc_style_amd.train_tgtcs --config configs/fern.txt --origin_train [--synthetic]`
+`python -m tgtc_style_amd.train_tgtcs --config configs/fern.txt --style_train [--synthetic]`
 
 The render half of the reference entry point (train_tgtcs.py:13-215): build the four networks and the latent
 table, reload the newest checkpoints, and dispatch to render_style / render_train_style (or cal_geometry with
@@ -9,8 +10,10 @@ rendering.py:216-217,363-364).
 Of the training half, `--origin_train` runs the reference's first stage, `Origin_train` (train_tgtcs.py:218-309), on the
 HIP training kernels: the NeRF pair is trained from the scene's images up to --origin_step, resuming from the newest
 NNNNNN.tar or starting fresh, and leaves the reference's checkpoint files (train_loop.py, train_data.py).  A mode the
-caller asks for: without the flag nothing trains.  The later stages (the 2-D module's training, `Style_train` and its VGG
-losses) are the reference's and stay out of this build.
+caller asks for: without the flag nothing trains.  `--style_train` runs `Style_train` (train_tgtcs.py:312-571): the two style
+MLPs and the latent table are trained on the frozen NeRF pair from the frames of `--render_train` and their stylised copies
+(train_loop.style_train), and leave style_NNNNNN.tar / latent_NNNNNN.tar for `--render_valid_style`.  The 2-D module's
+training and the VGG content / style losses are the reference's and stay out of this build.
 
 No dataset or checkpoint ships with this repository, so `--synthetic` provides a seeded scene: synth.nerf_state/...
 weights and a closed-form camera path (for --origin_train: a teacher scene rendered from those weights, and seeded
@@ -180,6 +183,39 @@ def _broadcast_from_rank0(t, dist):
         t.copy_(host)
 
 
+def _make_latents(args, device, sv_path, style_num, frame_num, stylized, world=1, dist=None):
+    """The latent table of a run: the newest latent checkpoint, else drawn around the VAE's encoding of the style
+    features, else (--synthetic) the seeded table (train_tgtcs.py:128-155)."""
+    latents = models.StyleLatents_variational(style_num=style_num, frame_num=frame_num,
+                                              latent_dim=args.vae_latent).to(device)
+    if not args.no_reload and checkpoints.load_latents(sv_path, latents):                  # train_tgtcs.py:139-146
+        pass
+    elif stylized is not None and style_num == stylized["style_num"] and os.path.exists(args.vae_pth_path):
+        # train_tgtcs.py:128-155: no latent checkpoint -> the VAE encodes the style features into mu / logvar and every
+        # frame's latent is drawn around them
+        vae = models.VAE(data_dim=1024, latent_dim=args.vae_latent, W=args.vae_w, D=args.vae_d, kl_lambda=args.vae_kl_lambda)
+        vae.load_state_dict(torch.load(args.vae_pth_path, map_location='cpu'))
+        vae.eval().to(device)
+        feats = torch.from_numpy(np.asarray(stylized["style_features"], np.float32)).to(device)
+        _, mu, logvar = vae.encode(feats)
+        latents.style_latents_mu = torch.nn.Parameter(mu.detach())
+        latents.style_latents_logvar = torch.nn.Parameter(logvar.detach())
+        latents.set_latents(generator=torch.Generator().manual_seed(args.latent_seed) if args.latent_seed >= 0 else None)
+        if world > 1:
+            # the draw comes from each process's own unseeded generator: rank 0's table is THE table, or the stripes / frames
+            # of different ranks would be rendered with different style latents
+            latents = latents.to(device)
+            for p in (latents.latents, latents.style_latents_mu, latents.style_latents_logvar):
+                _broadcast_from_rank0(p.data, dist)
+        print('Initializing Latent Model from', args.vae_pth_path)
+    elif args.synthetic:
+        latents.load_state_dict(_t(synth.latents_state(4, style_num=style_num, frame_num=frame_num)))
+    else:
+        raise SystemExit("train_tgtcs: no latent checkpoint in %s and no stylized_data.npz + --vae_pth_path to initialise "
+                         "the latents from (use --synthetic for the seeded scene)" % sv_path)
+    return latents.to(device)
+
+
 def _origin_train(args, device, sv_path, model, model_fine, concat_model, style_model):
     """--origin_train: the first stage of the reference's schedule (train_tgtcs.py:56-72,108-113,563-571) -> sv_path."""
     from . import train_data, train_loop
@@ -215,8 +251,57 @@ def _origin_train(args, device, sv_path, model, model_fine, concat_model, style_
                                                                          args.batch_size))
     end = train_loop.origin_train(args, model, model_fine, data, sv_path, first_step, optimizer_state=optimizer_state,
                                   style_optimizer=train_loop.make_style_optimizer(args, style_model, concat_model))
-    print('Origin_train done at step %d, checkpoints in %s.  The later stages (the 2-D module, Style_train) are the '
-          "reference's" % (end - 1, sv_path))
+    print('Origin_train done at step %d, checkpoints in %s.  Next: --render_train, the 2-D pass over its frames '
+          "(trans_test), then --style_train; training the 2-D module itself stays the reference's" % (end - 1, sv_path))
+    return sv_path
+
+
+def _style_train(args, device, sv_path, model, model_fine, concat_model, style_model):
+    """--style_train: the reference's Style_train stage (train_tgtcs.py:312-571) -> sv_path."""
+    from . import train_data, train_loop, trans_test
+    nerf_step = None if args.no_reload else checkpoints.load_nerf(sv_path, model, model_fine)      # train_tgtcs.py:60-72
+    if nerf_step is None:
+        if not args.synthetic:
+            raise SystemExit("train_tgtcs: --style_train needs the trained NeRF pair: no NeRF checkpoint in %s (run "
+                             "--origin_train first, or use --synthetic for the seeded scene)" % sv_path)
+        model.load_state_dict(_t(synth.nerf_state(0)))
+        model_fine.load_state_dict(_t(synth.nerf_state(1)))
+    elif int(nerf_step) + 1 < args.origin_step:
+        raise SystemExit("train_tgtcs: --style_train starts where Origin_train ends: the NeRF checkpoint in %s is of step "
+                         "%d, short of --origin_step %d (finish --origin_train first, or lower --origin_step)" % (
+                             sv_path, int(nerf_step), args.origin_step))
+    style_step = None if args.no_reload else checkpoints.load_style(sv_path, style_model, concat_model)   # :74-82
+    optimizer_state = None
+    if style_step is not None:
+        # as in _origin_train: the file holds the state AFTER iteration `style_step`, the run continues with the next one
+        first_step = int(style_step) + 1
+        optimizer_state = checkpoints.load_style_optimizer(sv_path)
+    else:
+        if args.synthetic:
+            concat_model.load_state_dict(_t(synth.concat_state(2)))
+            style_model.load_state_dict(_t(synth.style_state(3)))
+        first_step = int(nerf_step) + 1 if nerf_step is not None else 0
+    if first_step > args.total_step:
+        print('Style_train: global step %d has reached --total_step %d, nothing to train' % (first_step - 1, args.total_step))
+        return sv_path
+    if style_step is not None:
+        print('Resuming Style_train from the checkpoint of step %d in %s: continuing at step %d' % (int(style_step), sv_path, first_step))
+    else:
+        print('Style_train: no style checkpoint in %s, starting at step %d from %s' % (
+            sv_path, first_step, 'the seeded synthetic style networks' if args.synthetic else 'freshly initialised style networks'))
+    if args.synthetic:
+        data = train_data.StyleTrainRays.from_synthetic(args, device)
+        stylized = None
+    else:
+        data = train_data.StyleTrainRays.from_directories(args.datadir, args.factor, os.path.join(sv_path, 'nerf_gen_data2'),
+                                                          device, no_ndc=args.no_ndc, pixel_alignment=args.pixel_alignment)
+        stylized = trans_test.read_stylized_data(args.datadir, args.factor)
+    latents = _make_latents(args, device, sv_path, data.style_num, data.frame_num, stylized)
+    print('Style_train: %d style(s), %d frames of %d x %d, %d rows, %d per batch' % (
+        data.style_num, data.frame_num, data.h, data.w, data.data_num, args.batch_size_style))
+    end = train_loop.style_train(args, model, model_fine, concat_model, style_model, latents, data, sv_path, first_step,
+                                 optimizer_state=optimizer_state)
+    print('Style_train done at step %d, checkpoints in %s; --render_valid_style renders from them' % (end - 1, sv_path))
     return sv_path
 
 
@@ -231,7 +316,7 @@ def train(args):
                            'ImgFactor' + str(int(args.factor)))        # train_tgtcs.py:19-20
     os.makedirs(sv_path, exist_ok=True)
 
-    if args.origin_train and args.train_seed >= 0:
+    if (args.origin_train or args.style_train) and args.train_seed >= 0:
         torch.manual_seed(args.train_seed)      # a fresh start trains the default nn.Linear initialisation, as the reference
     model = models.StyleNerf(args, mode='coarse').to(device)
     model_fine = models.StyleNerf(args, mode='fine').to(device)
@@ -239,6 +324,8 @@ def train(args):
     style_model = models.StyleMLP_Wild_multilayers(args).to(device)
     if args.origin_train:
         return _origin_train(args, device, sv_path, model, model_fine, concat_model, style_model)
+    if args.style_train:
+        return _style_train(args, device, sv_path, model, model_fine, concat_model, style_model)
     global_step = 0
     step = None if args.no_reload else checkpoints.load_nerf(sv_path, model, model_fine)           # train_tgtcs.py:60-72
     nerf_step = -1 if step is None else int(step)      # part of the --geometry_cache keys (-1: the seeded synthetic weights)
@@ -281,34 +368,7 @@ def train(args):
     # a whole image (this rank's part of it) per call keeps the persistent kernels busy -- 78 calls of 2 048 rays cost a
     # 400x400 frame ~30 ms of launch gaps -- and gives the same pixels
     batch_size = args.batch_size if args.literal_batches else max(args.batch_size, dataset.rays_per_image())
-    latents = models.StyleLatents_variational(style_num=dataset.style_num, frame_num=dataset.frame_num,
-                                              latent_dim=args.vae_latent).to(device)
-    if not args.no_reload and checkpoints.load_latents(sv_path, latents):                  # train_tgtcs.py:139-146
-        pass
-    elif stylized is not None and dataset.style_num == stylized["style_num"] and os.path.exists(args.vae_pth_path):
-        # train_tgtcs.py:128-155: no latent checkpoint -> the VAE encodes the style features into mu / logvar and every
-        # frame's latent is drawn around them
-        vae = models.VAE(data_dim=1024, latent_dim=args.vae_latent, W=args.vae_w, D=args.vae_d, kl_lambda=args.vae_kl_lambda)
-        vae.load_state_dict(torch.load(args.vae_pth_path, map_location='cpu'))
-        vae.eval().to(device)
-        feats = torch.from_numpy(np.asarray(stylized["style_features"], np.float32)).to(device)
-        _, mu, logvar = vae.encode(feats)
-        latents.style_latents_mu = torch.nn.Parameter(mu.detach())
-        latents.style_latents_logvar = torch.nn.Parameter(logvar.detach())
-        latents.set_latents(generator=torch.Generator().manual_seed(args.latent_seed) if args.latent_seed >= 0 else None)
-        if world > 1:
-            # the draw comes from each process's own unseeded generator: rank 0's table is THE table, or the stripes / frames
-            # of different ranks would be rendered with different style latents
-            latents = latents.to(device)
-            for p in (latents.latents, latents.style_latents_mu, latents.style_latents_logvar):
-                _broadcast_from_rank0(p.data, dist)
-        print('Initializing Latent Model from', args.vae_pth_path)
-    elif args.synthetic:
-        latents.load_state_dict(_t(synth.latents_state(4, style_num=dataset.style_num, frame_num=dataset.frame_num)))
-    else:
-        raise SystemExit("train_tgtcs: no latent checkpoint in %s and no stylized_data.npz + --vae_pth_path to initialise "
-                         "the latents from (use --synthetic for the seeded scene)" % sv_path)
-    latents = latents.to(device)
+    latents = _make_latents(args, device, sv_path, dataset.style_num, dataset.frame_num, stylized, world, dist)
 
     renderer = rendering.RayRenderer(model, model_fine, models.StylePair(concat_model, style_model))
     common = dict(samp_func=utils.sampling_pts_uniform, model_forward=utils.batchify(lambda **kw: model(**kw), args.chunk),
@@ -342,9 +402,9 @@ def train(args):
                                    renderer=rendering.RayRenderer(model, model_fine), **common)
             print('Done, saving to', out)
             return out
-    raise SystemExit("train_tgtcs: nothing to do -- pass --render_valid_style, --render_train_style, --render_valid or "
-                     "--origin_train (of the reference's training stages only Origin_train is part of this build, and only "
-                     "when asked for)")
+    raise SystemExit("train_tgtcs: nothing to do -- pass --render_valid_style, --render_train_style, --render_valid, "
+                     "--render_train, --origin_train or --style_train (of the reference's training stages Origin_train and "
+                     "Style_train are part of this build, and only when asked for)")
 
 
 def _finish_distributed():
@@ -379,14 +439,18 @@ def main(argv=None):
             raise SystemExit("train_tgtcs: --style_precision fp16mx needs a --precision whose fine half is fp16mx, e.g. "
                              "fp16x3+fp16mx (got %s; the kernel runs the fine trunk and the style networks of a tile together)"
                              % args.precision)
-    if args.origin_train:
+    if args.origin_train and args.style_train:
+        raise SystemExit("train_tgtcs: --origin_train and --style_train are two stages: one call each, in that order")
+    for stage in ("origin_train", "style_train"):
+        if not getattr(args, stage):
+            continue
         renders = [f for f in ("render_valid", "render_train", "render_valid_style", "render_train_style") if getattr(args, f)]
         if renders:
-            raise SystemExit("train_tgtcs: --origin_train trains and returns; it does not go with --%s (render from the "
-                             "checkpoints in a second call)" % " / --".join(renders))
+            raise SystemExit("train_tgtcs: --%s trains and returns; it does not go with --%s (render from the "
+                             "checkpoints in a second call)" % (stage, " / --".join(renders)))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("train_tgtcs: --origin_train runs on one GPU (WORLD_SIZE = %s): the reference has no "
-                             "data-parallel training and neither has this build" % os.environ["WORLD_SIZE"])
+            raise SystemExit("train_tgtcs: --%s runs on one GPU (WORLD_SIZE = %s): the reference has no "
+                             "data-parallel training and neither has this build" % (stage, os.environ["WORLD_SIZE"]))
     if args.expname is None:
         raise SystemExit("train_tgtcs: --expname (or --config) is required")
     try:

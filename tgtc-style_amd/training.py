@@ -5,9 +5,13 @@ sampling with jitter, coarse NeRF, compositing with the density-noise regularise
 The networks must be marked `.trainable()` (models.StyleNerf): their forward then runs layer by layer on the differentiable
 HIP dense layers (autograd_ops.py) and `utils.alpha_composition` carries its own backward kernel.  The samplers carry no
 gradient, as in the reference (utils.py:562-579 detach).  The loop around `origin_train_step` -- shuffled batches, learning-rate decay,
-checkpoint cadence, logging -- is train_loop.origin_train (`train_tgtcs --origin_train`); the loop around
-`style_train_step` and the style stages' VGG losses are the reference's own training driver and stay outside this build
-(SURVEY section 8f rank 4)."""
+checkpoint cadence, logging -- is train_loop.origin_train (`train_tgtcs --origin_train`).
+
+`style_train_step` is the body of the reference's `Style_train` (train_tgtcs.py:352-482) batch by batch, as the reference
+runs it; `style_train_iteration` is the same iteration for the loop train_loop.style_train (`train_tgtcs --style_train`):
+both batches in one pass over the operators and the reference's two optimisers from one backward.  Both stay on the
+per-layer path for the two style MLPs (autograd_ops.py).  The VGG content / style losses of the reference's later stages
+and the training of the 2-D module stay outside this build."""
 import torch
 
 from . import utils
@@ -157,3 +161,82 @@ def style_train_step(model, model_fine, concat_model, style_model, latents, opti
     if loss_coh is not None:
         out['loss_coh'] = val(loss_coh)
     return out
+
+
+def style_train_iteration(model, model_fine, concat_model, style_model, latents, style_optimizer, latent_optimizer, batch, R,
+                          N_samples, N_samples_fine, near, far, coherence, sigma_noise_std=1.0, rgb_loss_lambda=1.0,
+                          logp_loss_lambda=0.0, loss_coh_lambda=0.0, coh_in_loss=True, data_type='llff', jitter=None,
+                          generator=None, check_ids=True, as_float=False):
+    """The same `Style_train` iteration as `style_train_step` with its coherence batch, for the loop
+    (train_loop.style_train): BOTH batches in ONE pass, and the reference's two optimisers from ONE backward.
+
+    batch: the dict of train_data.StyleTrainRays.batch -- rows [0, R) are the shuffled batch, rows [R, R + B) the
+    frame-ordered one.  All R + B rows go through sampling, the frozen NeRF passes, the style networks and compositing
+    together; every per-row quantity is independent of its neighbours, so the two batches are slices of the results.  The
+    iteration is bound by the host's enqueue, and this halves its launches.
+
+    The reference steps `style_optimizer` on loss_rgb + loss_logp + lambda_coh * loss_coh (on loss_rgb + loss_logp alone
+    once global_step > 122 000: coh_in_loss=False) and then `latents_model_1.optimize(loss)`, its own Adam([latents]) on
+    the gradient of loss_rgb + loss_logp alone (train_tgtcs.py:482-495, models.py:541-548).  Here the latents of the ordered
+    rows are gathered DETACHED: the coherence term then reaches the style networks only, loss_rgb + loss_logp depends on
+    the shuffled rows only, and one backward of the style optimiser's loss leaves exactly those two gradients -- the style
+    networks' from everything, the latent table's from loss_rgb + loss_logp.  style_latents_mu / _logvar are in neither
+    optimiser and do not move.
+
+    generator (a device torch.Generator): the stratified jitter [R+B, N_samples] (unless `jitter` is given), then the
+    density-noise plane of the coarse pass [R+B, N_samples], then that of the fine pass [R+B, N_samples+N_samples_fine],
+    are drawn from it in that order.  check_ids=False skips the latent table's id check and its read-back (ids from the
+    batch kernel and an in-range sampler).  -> dict loss, loss_rgb, loss_logp, loss_coh (unweighted), total (the style
+    optimiser's loss), detached device scalars unless as_float."""
+    ro, rd = batch['rays_o'], batch['rays_d']
+    sid, fid = batch['style_id'], batch['frame_id']
+    T = ro.shape[0]
+    noise = lambda n: None
+    if generator is not None:
+        if jitter is None:
+            jitter = torch.rand(T, N_samples, device=ro.device, generator=generator)
+        if sigma_noise_std > 0:
+            noise = lambda n: torch.randn(T, n, device=ro.device, generator=generator) * sigma_noise_std
+    z = latents(style_ids=sid[:R], frame_ids=fid[:R], type=data_type, check_ids=check_ids)
+    if T > R:
+        with torch.no_grad():
+            z2 = latents(style_ids=sid[R:], frame_ids=fid[R:], type=data_type, check_ids=check_ids)
+        z = torch.cat((z, z2), dim=0)
+    zbar = torch.mean(z, dim=1, keepdim=True)
+    L = z.shape[-1]
+
+    def one_pass(nerf, pts, n):
+        with torch.no_grad():
+            ret = nerf(pts=pts, dirs=rd.unsqueeze(1).expand([T, n, 3]))
+        cf = concat_model(x=ret['pts'], latent=z.unsqueeze(1).expand([T, n, L]))['concat_features']
+        both = torch.cat((ret['base_remap'], cf), dim=-1)
+        rgb = style_model(x=ret['pts'], concated=both, latent=zbar.unsqueeze(2).expand([T, n, L]))['rgb']
+        return rgb, ret['sigma']
+
+    pts, ts = utils.sampling_pts_uniform(rays_o=ro, rays_d=rd, N_samples=N_samples, near=near, far=far, perturb=True, jitter=jitter)
+    rgb, sigma = one_pass(model, pts, N_samples)
+    rgb_exp, _, weights = utils.alpha_composition(rgb, sigma, ts, sigma_noise_std, noise=noise(N_samples))
+    rgb_gt, rgb_origin2 = batch['rgb_gt'][:R], batch['rgb_origin'][R:]
+    loss_rgb = rgb_loss_lambda * img2mse(rgb_exp[:R], rgb_gt)
+    loss_coh = coherence.coarse(rgb_exp[R:], rgb_origin2) if T > R else rgb_exp.new_zeros(())
+    if N_samples_fine > 0:
+        n = N_samples + N_samples_fine
+        pts_f, ts_f = utils.sampling_pts_fine_torch(ro, rd, ts, weights.detach(), N_samples_fine)
+        rgb, sigma = one_pass(model_fine, pts_f, n)
+        rgb_exp_fine, _, _ = utils.alpha_composition(rgb, sigma, ts_f, sigma_noise_std, noise=noise(n))
+        loss_rgb = loss_rgb + rgb_loss_lambda * img2mse(rgb_exp_fine[:R], rgb_gt)
+        if T > R:
+            loss_coh = loss_coh + coherence.fine(rgb_exp_fine[R:], rgb_origin2)
+    loss_logp = logp_loss_lambda * latents.minus_logp(style_ids=sid[:R], frame_ids=fid[:R], data_type=data_type, check_ids=check_ids)
+    loss = loss_rgb + loss_logp
+    total = loss + loss_coh_lambda * loss_coh if coh_in_loss else loss
+    style_optimizer.zero_grad()
+    if latent_optimizer is not None:
+        latent_optimizer.zero_grad()
+    total.backward()
+    style_optimizer.step()
+    if latent_optimizer is not None:
+        latent_optimizer.step()
+    val = (lambda t: float(t.detach())) if as_float else (lambda t: t.detach())
+    return {'loss': val(loss), 'loss_rgb': val(loss_rgb), 'loss_logp': val(loss_logp), 'loss_coh': val(loss_coh),
+            'total': val(total)}
