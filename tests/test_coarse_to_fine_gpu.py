@@ -2,8 +2,12 @@
 render: tgtc_composite (zero colours, weights out) followed by tgtc_sample_fine.  Every comparison is of BITS.
 
 R = 9: the kernel takes four rays per workgroup, so two full workgroups and a tail of one ray.
-Shapes (N, n_fine): (3, 1) the smallest; (16, 16); (64, 64) and (66, 64), the last N with one pdf entry per lane of the cdf
-scan; (67, 5), the first with two; (128, 64) the frame's; (256, 256) both limits (N = 256, N + n_fine = 512).
+Shapes (N, n_fine): (3, 1) the smallest, one new sample at u = 0; (3, 2); (16, 16); (64, 64) and (66, 64), the last N with one
+pdf entry per lane of the cdf scan; (67, 5), the first with two; (128, 64) the frame's; (130, 3) the last with two; (195, 7)
+the first with four; (256, 1); (256, 256) both limits (N = 256, N + n_fine = 512).
+
+Every output plane is pre-filled with CANARY, a NaN bit pattern, and compared by bits: a slot that no lane wrote fails the
+`isfinite` assertions on the pair's outputs.
 
 Which path a ray takes is reported by tgtc_coarse_to_fine_traced and asserted for every case: MERGE_DEPTHS are the depth
 rows whose rays must all take the merge; in "descending" ray DESC_ROW -- its coarse depths descend -- must take the counting
@@ -13,15 +17,15 @@ import numpy as np
 import pytest
 import torch
 
+from sampler_cases import DESC_ROW, R, depth_rows      # R = 9, DESC_ROW = 4
+
 pytestmark = pytest.mark.gpu
 
-R = 9
-SHAPES = [(3, 1), (16, 16), (64, 64), (66, 64), (67, 5), (128, 64), (256, 256)]
+SHAPES = [(3, 1), (3, 2), (16, 16), (64, 64), (66, 64), (67, 5), (128, 64), (130, 3), (195, 7), (256, 1), (256, 256)]
 SIGMAS = ["random", "dead", "saturated", "constant"]
 MERGE_DEPTHS = ["linspace", "jittered", "ties"]
 DEPTHS = MERGE_DEPTHS + ["descending"]
-DESC_ROW = 4
-CANARY = -7.25
+CANARY = 0x7FC0BEEF          # a quiet NaN, as int32
 
 
 def sigma_plane(kind, N, rng):
@@ -40,24 +44,8 @@ def sigma_plane(kind, N, rng):
     return s, rand
 
 
-def depth_rows(kind, N, rng):
-    lin = np.linspace(0.0, 1.0, N, dtype=np.float32)
-    if kind == "linspace":
-        return np.tile(lin, (R, 1))
-    jit = np.sort(lin[None, :] + rng.uniform(-0.4, 0.4, (R, N)).astype(np.float32) / N, axis=1).astype(np.float32)
-    if kind == "jittered":
-        return jit
-    if kind == "ties":                                                # repeated coarse depths: pairs and one triple per ray
-        ts = jit.copy()
-        ts[:, 1] = ts[:, 0] if N > 3 else ts[:, 2]
-        for k in range(5, N - 2, 7):
-            ts[:, k] = ts[:, k - 1]
-        if N >= 16:
-            ts[:, N // 2] = ts[:, N // 2 + 1] = ts[:, N // 2 - 1]
-        return ts
-    ts = jit.copy()
-    ts[DESC_ROW] = ts[DESC_ROW, ::-1]
-    return ts
+def canary_plane(rows, cols):
+    return torch.full((rows, cols), CANARY, dtype=torch.int32, device="cuda").view(torch.float32)
 
 
 def bits(t):
@@ -83,8 +71,8 @@ def case(N, NF, skind, dkind):
         rd = torch.ones(R, 3, dtype=torch.float64, device="cuda")
         rgb = torch.zeros(R, N, 3, device="cuda")
         rgb_exp, t_exp = torch.empty(R, 3, device="cuda"), torch.empty(R, device="cuda")
-        w = torch.full((R + 1, N), CANARY, device="cuda")
-        out = torch.full((R + 1, N + NF), CANARY, device="cuda")
+        w = canary_plane(R + 1, N)
+        out = canary_plane(R + 1, N + NF)
         hip.check(lib.tgtc_composite(hip.ptr(rgb), hip.ptr(sigma), hip.ptr(ts), R, N, hip.ptr(rgb_exp), hip.ptr(t_exp), hip.ptr(w),
                                      hip.stream()))
         hip.check(lib.tgtc_sample_fine(hip.ptr(ro), hip.ptr(rd), hip.ptr(ts), hip.ptr(w), R, N, NF, None, hip.ptr(out),
@@ -103,8 +91,8 @@ def test_bits_of_composite_then_sample_fine(N, NF, skind, dkind):
     lib = hip.load()
     sigma, ts, w_ref, out_ref = case(N, NF, skind, dkind)
     for with_weights in (True, False):
-        w = torch.full((R + 1, N), CANARY, device="cuda")
-        out = torch.full((R + 1, N + NF), CANARY, device="cuda")
+        w = canary_plane(R + 1, N)
+        out = canary_plane(R + 1, N + NF)
         took = torch.full((R + 1,), 77, dtype=torch.int32, device="cuda")
         hip.check(lib.tgtc_coarse_to_fine_traced(hip.ptr(sigma), hip.ptr(ts), R, N, NF, hip.ptr(out),
                                                  hip.ptr(w) if with_weights else None, hip.ptr(took), hip.stream()))
@@ -113,13 +101,13 @@ def test_bits_of_composite_then_sample_fine(N, NF, skind, dkind):
         if with_weights:
             assert torch.equal(bits(w), bits(w_ref))
         else:
-            assert bool((w == CANARY).all())                               # no plane given: nothing written
+            assert bool((bits(w) == CANARY).all())                         # no plane given: nothing written
         want = [0] * R + [77]
         if dkind == "descending":
             want[DESC_ROW] = 1
         assert took.tolist() == want, (N, NF, skind, dkind, took.tolist())
     # the entry point without the trace is the same launch
-    out = torch.full((R + 1, N + NF), CANARY, device="cuda")
+    out = canary_plane(R + 1, N + NF)
     hip.check(lib.tgtc_coarse_to_fine(hip.ptr(sigma), hip.ptr(ts), R, N, NF, hip.ptr(out), None, hip.stream()))
     torch.cuda.synchronize()
     assert torch.equal(bits(out), bits(out_ref))

@@ -125,10 +125,10 @@ def test_sample_fine_golden(golden):
         pts, tv = utils.sampling_pts_fine_torch(ro, rd, ts, w, 64)
         assert tv.shape == (ro.shape[0], N + 64)
         assert bool((tv[:, 1:] >= tv[:, :-1]).all())
-        # cdf: float64 running sum like ATen's CPU cumsum, but the float32 normaliser (sum of weights) is
-        # reduced in a different order -> pdf differs by ~1 ulp; a sample at cdf position u moves by
-        # d(cdf)/pdf, and pdf is as small as 1e-5/sum in empty bins: |dt| <~ 1e-7/1e-5 * bin(1/64) ~ 2e-4 worst
-        # case, typically < 1e-6.
+        # cdf: float64 running sum like ATen's CPU cumsum.  The normaliser (sum of weights) is summed in float64 and
+        # rounded once, where the reference's float32 torch.sum rounds its partial sums -> the normaliser, and with it
+        # every pdf entry, differs by ~1 ulp; a sample at cdf position u moves by d(cdf)/pdf, and pdf is as small as
+        # 1e-5/sum in empty bins: |dt| <~ 1e-7/1e-5 * bin(1/64) ~ 2e-4 worst case, typically < 1e-6.
         d = (tv.double().cpu() - torch.from_numpy(g["tvals" + tag]).double()).abs()
         assert float(d.max()) <= 2e-4, float(d.max())
         assert float(d.median()) <= 1e-7

@@ -16,7 +16,9 @@ namespace tgtc {
 
 __device__ __forceinline__ float linspace01(int i, int n) {
     // torch.linspace(0,1,n) float32 (ATen RangeFactoriesKernel: first half start+step*i, second half
-    // end-step*(n-1-i), each with a single rounding).
+    // end-step*(n-1-i), each with a single rounding).  n = 1 is [start] = [0]: the step below would be 1/0 and the
+    // second-half formula -inf * 0 + 1 = NaN.
+    if (n < 2) return 0.0f;
     const float step = 1.0f / (float)(n - 1);
     return (i < n / 2) ? step * (float)i : __fmaf_rn(-step, (float)(n - 1 - i), 1.0f);
 }
