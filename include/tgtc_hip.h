@@ -254,6 +254,62 @@ int tgtc_nerf_stash_fill(const tgtc_net* net, const double* rays_o, const double
 int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N,
                           uint32_t* scratch, float* rgb, void* stream);
 
+/* ------------------------------------------------------------------ density screen of the plain chain
+ * All a frame takes from a density is relu(sigma): a sample with sigma <= 0 has alpha 0 and weight +0 exactly, in the coarse
+ * weights that feed the inverse CDF and in the fine composite.  A NeRF handle in TGTC_PREC_FP16X3 or TGTC_PREC_FP16_FP6 can
+ * carry its weights a second time, in the form tgtc_nerf_create packs for TGTC_PREC_FP16 (an allocation of its own), and a
+ * margin m.  A SCREENED pass of tgtc_render_rays_plain on TGTC_PATH_CHAIN is then: the fp16 sigma-only launch over all
+ * samples; the compaction of the candidates (screen density not <= -m; NaN and +inf are candidates) into an ascending
+ * device-side list; the pass's exact kernel over that list alone.  While |sigma_screen - sigma_exact| < m every sample the
+ * list leaves out has sigma_exact < 0, and the frame has the BITS of the dense pass.
+ *   coarse pass: when no coarse image is asked and the coarse handle (fp16x3) has a screen; the exact densities of the
+ *                candidates from tgtc_nerf_sigma_list.  List + scratch live in the fine colour plane (dense where
+ *                R x (n_coarse + n_fine) x 12 bytes < R x n_coarse x 4 + 8192).
+ *   fine pass:   a fine handle in fp16mx with a screen; density AND colour of the candidates from
+ *                tgtc_nerf_forward_list_sigma, the compositor of the two-phase pass.  List + scratch live where the
+ *                two-phase pass keeps its list; no stash is used.  Counts in tgtc_net_culled_renders; TGTC_CULL_OFF on the
+ *                handle switches it off as well.
+ * tgtc_render_workspace_bytes is what it was; there is no host synchronisation in a render.
+ * tgtc_net_enable_screen(net, stream): packs the fp16 form and calibrates the margin -- screen and exact sigma-only launches
+ *   on 256 fixed host-generated rays (origins uniform in [-1.5, 1.5]^2 x {-1}, directions (u, v, 2) with u, v uniform in
+ *   [-1, 1]) x 128 depths equally spaced on [0, 1]; m = 8 x max |sigma_screen - sigma_exact|.  ONE host synchronisation, a host
+ *   call like packing.  Idempotent.  A zero or non-finite calibration error leaves the screen disabled (TGTC_OK; the handle
+ *   renders as before).  Style handles and TGTC_PREC_FP16 handles -> TGTC_ERR_UNSUPPORTED; NULL -> TGTC_ERR_ARG.
+ * tgtc_net_screen_margin: m, or -1 when no screen is enabled (and for NULL).
+ * tgtc_net_set_screen: the policy of the passes this handle is screened in.
+ *   TGTC_SCREEN_AUTO (default)  screen iff the candidate share of the last such pass THAT HAS LANDED in the handle's pinned
+ *                               word is below the pass's threshold; unknown: not screened.  Read without waiting.
+ *   TGTC_SCREEN_OFF             never (and no statistic is taken).
+ *   TGTC_SCREEN_ON              wherever the list fits.
+ *   "Not screened" is the pass as it was: in the fine pass whatever TGTC_CULL_* and the stash decide.
+ *   TGTC_ERR_ARG for a bad mode or a handle that is not a NeRF handle, TGTC_ERR_UNSUPPORTED for a TGTC_PREC_FP16 handle.
+ * tgtc_net_screen_fraction: the candidate share that has landed (from the compaction's count in a screened pass, from one run
+ *   of the count kernel at -m over the exact densities otherwise), or -1 while none has.
+ * tgtc_net_screened_renders: how many chain renders screened their pass with this handle (-1 for NULL / no screen state).
+ * tgtc_screen_list_fits / tgtc_screen_auto_decision: the two rules as pure host functions -- does a list of up to M indices
+ *   and the 8192-byte scratch fit `bytes`; does AUTO screen pass 0 (coarse) / 1 (fine) on a landed (candidates, total).
+ * The launches as entries of their own (tests, tools):
+ *   tgtc_nerf_screen_rays: sigma [R,N] from the screen form (TGTC_ERR_UNSUPPORTED without a screen).
+ *   tgtc_nerf_sigma_list: sigma[s] of the listed samples, the bits of tgtc_nerf_forward_rays(rgb = NULL), nothing else
+ *     touched; TGTC_PREC_FP16X3 handles only (csrc/mlp_nerf_x3s.hip, the IN_LIST instance).  List rules as tgtc_nerf_forward_list.
+ *   tgtc_nerf_forward_list_sigma: tgtc_nerf_forward_list that also writes sigma[s] of the listed samples. */
+#define TGTC_SCREEN_AUTO 0
+#define TGTC_SCREEN_OFF 1
+#define TGTC_SCREEN_ON 2
+int tgtc_net_enable_screen(tgtc_net* net, void* stream);
+float tgtc_net_screen_margin(const tgtc_net* net);
+int tgtc_net_set_screen(tgtc_net* net, int mode);
+float tgtc_net_screen_fraction(const tgtc_net* net);
+long long tgtc_net_screened_renders(const tgtc_net* net);
+int tgtc_screen_list_fits(size_t bytes, int64_t M);
+int tgtc_screen_auto_decision(int pass, uint32_t candidates, uint32_t total);
+int tgtc_nerf_screen_rays(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                          float* sigma, void* stream);
+int tgtc_nerf_sigma_list(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         const uint32_t* live, const uint32_t* n_live, float* sigma, void* stream);
+int tgtc_nerf_forward_list_sigma(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                                 int N, const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, void* stream);
+
 /* ------------------------------------------------------------------ a8: latent table
  * models.py:490-506 StyleLatents_variational.forward.  latents float [S,F,D] device, mu float [S,D] device,
  * style_ids / frame_ids int64 [R] device.  tile7: the llff `repeat((7,1))` wrap (models.py:496).

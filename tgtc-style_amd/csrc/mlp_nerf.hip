@@ -297,15 +297,39 @@ int nerf_forward_rays_impl(const tgtc_net* net, const double* rays_o, const doub
     return rgb ? dispatch_nerf<IN_RAYS, true>(net, a, st) : dispatch_nerf<IN_RAYS, false>(net, a, st);
 }
 
-// rgb[live[i]] for the *n_live samples of a device-side list (the caller has checked the precision and R x N < 2^31)
+// rgb[live[i]] -- and sigma[live[i]] where sigma is given -- for the *n_live samples of a device-side list (the caller has
+// checked the precision and R x N < 2^31)
 int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
-                           const uint32_t* live, const uint32_t* n_live, float* rgb, hipStream_t st) {
+                           const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st) {
     NerfArgs a{};
-    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.rgb = rgb;
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.rgb = rgb, a.sigma = sigma;
     a.live = live, a.n_live = n_live;
     a.bias = net->dev;
     a.stream = net->dev + net->bias_bytes;
     return nerf_mx_launch(IN_LIST, true, a, st);
+}
+
+// sigma[live[i]] for the *n_live samples of a device-side list, fp16x3 handles: the bits of the sigma-only launch over rays
+// (the caller has checked the precision and R x N < 2^31)
+int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.sigma = sigma;
+    a.live = live, a.n_live = n_live;
+    a.bias = net->dev;
+    a.stream = net->dev + net->bias_bytes;
+    return nerf_x3s_list_launch(a, st);
+}
+
+// The density screen: sigma of every sample from the handle's TGTC_PREC_FP16 form, one MFMA product per
+// weight -- the sigma-only launch an fp16 handle runs (the caller has checked that the screen is enabled)
+int nerf_screen_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                          float* sigma, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.sigma = sigma;
+    a.bias = net->screen->dev;
+    a.stream = net->screen->dev + kNerfBiasBytes;
+    return launch_nerf<CfgFast, IN_RAYS, false>(a, st);
 }
 
 // ---- the stashed two-phase fine pass (mlp_nerf_mx2_stash.hip).  scratch: kSparseScratchBytes laid out as the compaction's
@@ -422,8 +446,152 @@ extern "C" int tgtc_nerf_create(const tgtc_linear* layers, int n_layers, int pre
         delete net;
         return fail(TGTC_ERR_HIP, "nerf_create: hipMemcpy: %s", hipGetErrorString(e));
     }
+    if (precision != TGTC_PREC_FP16) {
+        // what tgtc_net_enable_screen packs from (vectors keep their buffers when moved: eq.lin still points into them)
+        net->screen = new tgtc_screen_state();
+        net->screen->eq = std::move(eq);
+    }
     *out = net;
     return TGTC_OK;
+}
+
+// ---- the density screen of a handle
+namespace {
+// the calibration's rays: a fixed 64-bit generator (splitmix64), so that a handle's margin is a function of its weights alone
+struct ScreenRng {
+    uint64_t s;
+    double uniform() {   // [0, 1)
+        uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+    }
+};
+constexpr int kScreenCalRays = 256, kScreenCalDepths = 128;
+constexpr float kScreenMarginFactor = 8.0f;
+
+struct DeviceBuf {   // freed on every way out of the calibration
+    void* p = nullptr;
+    ~DeviceBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+extern "C" int tgtc_net_enable_screen(tgtc_net* net, void* stream) {
+    TGTC_REQUIRE(net, "net_enable_screen: null handle");
+    if (net->kind != 0 || net->precision == TGTC_PREC_FP16 || !net->screen)
+        return fail(TGTC_ERR_UNSUPPORTED, "net_enable_screen: built for NeRF handles in fp16x3 or fp16mx (an fp16 handle is its own screen)");
+    tgtc_screen_state* const s = net->screen;
+    if (s->dev) return TGTC_OK;
+    // 1. the TGTC_PREC_FP16 form of the handle's equalised layers: tgtc_nerf_create's bias table and stream for that precision
+    PackedNet p = pack_layers(nerf_specs(s->eq.lin.data()), false);
+    if (p.n_frags != NerfLayout::kFragsFull || (int)p.bias.size() != NerfLayout::kBiasFloats)
+        return fail(TGTC_ERR_UNSUPPORTED, "net_enable_screen: internal layout mismatch (%d frags, %zu bias)", p.n_frags, p.bias.size());
+    const size_t stream_bytes = p.stream.size() * sizeof(half_t), total = kNerfBiasBytes + stream_bytes + kRingBytes;
+    std::vector<char> host(total, 0);
+    std::memcpy(host.data(), p.bias.data(), p.bias.size() * sizeof(float));
+    std::memcpy(host.data() + kNerfBiasBytes, p.stream.data(), stream_bytes);
+    DeviceBuf form;
+    TGTC_HIP_CHECK(hipMalloc(&form.p, total));
+    TGTC_HIP_CHECK(hipMemcpy(form.p, host.data(), total, hipMemcpyHostToDevice));
+    // 2. the calibration: screen and exact densities of 256 fixed rays x 128 depths on [0, 1]
+    constexpr int R = kScreenCalRays, N = kScreenCalDepths;
+    std::vector<double> rays(2 * R * 3);
+    std::vector<float> ts((size_t)R * N);
+    ScreenRng rng{0x7467746373637265ull};
+    for (int r = 0; r < R; ++r) {
+        double* o = &rays[r * 3], *d = &rays[(R + r) * 3];
+        o[0] = 3.0 * rng.uniform() - 1.5, o[1] = 3.0 * rng.uniform() - 1.5, o[2] = -1.0;
+        d[0] = 2.0 * rng.uniform() - 1.0, d[1] = 2.0 * rng.uniform() - 1.0, d[2] = 2.0;
+        for (int i = 0; i < N; ++i) ts[(size_t)r * N + i] = (float)i / (float)(N - 1);
+    }
+    DeviceBuf d_rays, d_ts, d_sigma;
+    TGTC_HIP_CHECK(hipMalloc(&d_rays.p, rays.size() * sizeof(double)));
+    TGTC_HIP_CHECK(hipMalloc(&d_ts.p, ts.size() * sizeof(float)));
+    TGTC_HIP_CHECK(hipMalloc(&d_sigma.p, 2 * ts.size() * sizeof(float)));
+    TGTC_HIP_CHECK(hipMemcpy(d_rays.p, rays.data(), rays.size() * sizeof(double), hipMemcpyHostToDevice));
+    TGTC_HIP_CHECK(hipMemcpy(d_ts.p, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice));
+    hipStream_t st = as_stream(stream);
+    const double* const ro = static_cast<const double*>(d_rays.p);
+    float* const sig = static_cast<float*>(d_sigma.p);
+    s->dev = static_cast<char*>(form.p);   // (nerf_screen_rays_impl reads it; taken back below where the calibration fails)
+    int rc = nerf_screen_rays_impl(net, ro, ro + R * 3, static_cast<const float*>(d_ts.p), R, N, sig, st);
+    s->dev = nullptr;
+    if (rc) return rc;
+    rc = nerf_forward_rays_impl(net, ro, ro + R * 3, static_cast<const float*>(d_ts.p), R, N, nullptr, sig + ts.size(), st);
+    if (rc) return rc;
+    TGTC_HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<float> sigma(2 * ts.size());
+    TGTC_HIP_CHECK(hipMemcpy(sigma.data(), sig, sigma.size() * sizeof(float), hipMemcpyDeviceToHost));
+    float err = 0.0f;
+    bool finite = true;
+    for (size_t i = 0; i < ts.size(); ++i) {
+        const float e = std::fabs(sigma[i] - sigma[ts.size() + i]);
+        finite = finite && std::isfinite(e);
+        err = std::fmax(err, e);
+    }
+    const float margin = kScreenMarginFactor * err;
+    // a network whose two forms agree exactly (a constant density) or whose densities are not finite has no margin to
+    // screen by: the screen stays disabled and the handle renders as it did
+    if (!finite || !(err > 0.0f) || !std::isfinite(margin)) return TGTC_OK;
+    if (!s->landed) {
+        void* word = nullptr;
+        TGTC_HIP_CHECK(hipHostMalloc(&word, sizeof(uint64_t), hipHostMallocDefault));
+        *static_cast<uint64_t*>(word) = 0;
+        s->landed = static_cast<volatile uint64_t*>(word);
+    }
+    s->margin = margin;
+    s->dev = static_cast<char*>(form.p);
+    form.p = nullptr;
+    return TGTC_OK;
+}
+
+extern "C" float tgtc_net_screen_margin(const tgtc_net* net) {
+    return net && net->screen && net->screen->dev ? net->screen->margin : -1.0f;
+}
+
+extern "C" int tgtc_net_set_screen(tgtc_net* net, int mode) {
+    TGTC_REQUIRE(net && net->kind == 0, "net_set_screen: not a NeRF handle");
+    TGTC_REQUIRE(mode == TGTC_SCREEN_AUTO || mode == TGTC_SCREEN_OFF || mode == TGTC_SCREEN_ON, "net_set_screen: bad mode %d", mode);
+    if (!net->screen) return fail(TGTC_ERR_UNSUPPORTED, "net_set_screen: an fp16 handle has no screen");
+    net->screen->mode = mode;
+    return TGTC_OK;
+}
+
+extern "C" float tgtc_net_screen_fraction(const tgtc_net* net) {
+    if (!net || !net->screen || !net->screen->landed) return -1.0f;
+    const uint64_t word = *net->screen->landed;   // one aligned 8-byte read: never half of a copy
+    const uint32_t cand = (uint32_t)word, total = (uint32_t)(word >> 32);
+    if (total == 0 || cand > total) return -1.0f;
+    return (float)((double)cand / (double)total);
+}
+
+extern "C" long long tgtc_net_screened_renders(const tgtc_net* net) { return net && net->screen ? net->screen->screened : -1; }
+
+extern "C" int tgtc_nerf_screen_rays(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                                     int N, float* sigma, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_screen_rays: bad argument");
+    if (!(net->screen && net->screen->dev))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_screen_rays: the handle has no screen (tgtc_net_enable_screen)");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && sigma, "nerf_screen_rays: null pointer");
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_screen_rays: R x N >= 2^31 (chunk the rays)");
+    return nerf_screen_rays_impl(net, rays_o, rays_d, ts, R, N, sigma, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_sigma_list(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                                    int N, const uint32_t* live, const uint32_t* n_live, float* sigma, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_sigma_list: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && live && n_live && sigma, "nerf_sigma_list: null pointer");
+    if (net->precision != TGTC_PREC_FP16X3)
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_sigma_list: built for fp16x3 handles only (got precision %d)", net->precision);
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_sigma_list: R x N >= 2^31 (chunk the rays)");
+    return nerf_sigma_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, sigma, as_stream(stream));
 }
 
 extern "C" int tgtc_net_destroy(tgtc_net* net) {
@@ -436,6 +604,11 @@ extern "C" int tgtc_net_destroy(tgtc_net* net) {
     if (net->mx) {
         if (net->mx->dev) (void)hipFree(net->mx->dev);
         delete net->mx;
+    }
+    if (net->screen) {
+        if (net->screen->dev) (void)hipFree(net->screen->dev);
+        if (net->screen->landed) (void)hipHostFree(const_cast<uint64_t*>(net->screen->landed));
+        delete net->screen;
     }
     delete net;
     if (e != hipSuccess) return fail(TGTC_ERR_HIP, "net_destroy: hipFree: %s", hipGetErrorString(e));
@@ -553,6 +726,19 @@ extern "C" int tgtc_nerf_forward_list(const tgtc_net* net, const double* rays_o,
         return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list: built for fp16+fp6 handles only (got precision %d)", net->precision);
     if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
         return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list: R x N >= 2^31 (chunk the rays)");
-    return nerf_forward_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, as_stream(stream));
+    return nerf_forward_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, nullptr, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_forward_list_sigma(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts,
+                                            int64_t R, int N, const uint32_t* live, const uint32_t* n_live, float* rgb,
+                                            float* sigma, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_forward_list_sigma: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && live && n_live && rgb && sigma, "nerf_forward_list_sigma: null pointer");
+    if (net->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list_sigma: built for fp16+fp6 handles only (got precision %d)", net->precision);
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list_sigma: R x N >= 2^31 (chunk the rays)");
+    return nerf_forward_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, sigma, as_stream(stream));
 }
 #endif  // TGTC_TU_FP16_ONLY

@@ -38,5 +38,7 @@ int nerf_mx2_stash_launch(const NerfArgs& a, const NerfStashArgs& s, hipStream_t
 int nerf_mx2_heads_launch(const NerfArgs& a, const NerfStashArgs& s, hipStream_t st);
 // fp16x3, rays in, sigma out (the coarse pass): two column tiles per wave, one wave per SIMD, persistent (mlp_nerf_x3s.hip)
 int nerf_x3s_launch(const NerfArgs& a, hipStream_t st);
+// the same over a device-side list (a.live, a.n_live): sigma[live[slot]], nothing else
+int nerf_x3s_list_launch(const NerfArgs& a, hipStream_t st);
 
 }  // namespace tgtc

@@ -25,7 +25,8 @@ using CfgMx2 = MlpCfg<4, 2, false, 4>;
 // FULL = false: the trunk + sigma head alone (the coarse pass of a render whose coarse network is fp16mx), rays in, densities out
 // IN_LIST (the colour phase of the two-phase fine pass, render.hip): pass p owns list slots [128 p, 128 p + 128); the number
 // of passes follows from *n_live read HERE (the host's n_pass is ignored, the grid is the CU count), a workgroup without
-// a pass still runs the ring prologue and the final wait; only rgb is stored, scattered to rgb[live[slot]].
+// a pass still runs the ring prologue and the final wait; rgb is stored, scattered to rgb[live[slot]], and -- where a.sigma
+// is set -- sigma to sigma[live[slot]].
 template <int IN_MODE, bool FULL>
 __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long n_pass) {
     using C = CfgMx2;
@@ -112,6 +113,7 @@ __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long 
                     if (slot < n_live) {
                         const unsigned s = a.live[slot];
                         if (s < a.M) {   // (a list that keeps its promise never fails this)
+                            if (a.sigma) a.sigma[s] = sigma[c];   // (the screened fine pass: the candidates' exact densities)
 #pragma unroll
                             for (int r = 0; r < 3; ++r) a.rgb[(size_t)s * 3 + r] = 1.0f / (1.0f + expf(-rgb[c][r]));   // models.py:111
                         }

@@ -20,8 +20,17 @@ using CfgX3s = MlpCfg<4, 2, true, 4>;
 #define TGTC_FRONT_ABL 0
 #endif
 
+// IN_LIST (the exact phase of the screened coarse pass, render.hip): pass p owns list slots [128 p, 128 p + 128); the number
+// of passes follows from *n_live read HERE (the host's n_pass is ignored, the grid is the CU count), a workgroup without a
+// pass still runs the ring prologue and the final wait; sigma is scattered to sigma[live[slot]], slots past the end are masked.
+template <int IN_MODE>
 __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long n_pass) {
     using C = CfgX3s;
+    unsigned n_live = 0;   // IN_LIST only; a scalar load, issued before any LDS-DMA
+    if constexpr (IN_MODE == IN_LIST) {
+        n_live = __builtin_amdgcn_readfirstlane(*a.n_live);
+        n_pass = ((long long)n_live + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;
+    }
     using Ring = WeightStream<C, SingleStreamMap<NerfLayout::kFragsSigma>, true, true>;
     // the stream's ring: 128 KiB in chunks of kX3sChunkBytes (the generator's `chunk`), every wave moves 1/4 of a chunk
     constexpr int kChunk = kX3sChunkBytes, kSlots = C::RING_BYTES / kChunk, kLook = kSlots - 1, kPiece = kChunk / C::NWAVES;
@@ -68,7 +77,8 @@ __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long 
             for (int c = 0; c < 2; ++c)
                 pe_h[0][c] = pe_h[1][c] = pe_l[0][c] = pe_l[1][c] = half8{(_Float16)(float)(pos[c][0] + pos[c][1] + pos[c][2])};
 #else
-            nerf_load_samples<2, IN_RAYS>(a, s_wave, n, pos, dir, sidx);
+            if constexpr (IN_MODE == IN_LIST) nerf_load_samples<2, IN_LIST>(a, s_wave, n, pos, dir, sidx, n_live);
+            else nerf_load_samples<2, IN_RAYS>(a, s_wave, n, pos, dir, sidx);
             nerf_encode<2, true, false>(a, pos, dir, sidx, g, pe_h, pe_l, de_h, de_l);
 #endif
 #pragma unroll
@@ -86,6 +96,15 @@ __global__ void __launch_bounds__(256, 1) nerf_x3s_kernel(NerfArgs a, long long 
         if (lane < 16) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
+                if constexpr (IN_MODE == IN_LIST) {
+                    // the slot's sample is read again here: nothing but scalars lives across the stream
+                    const unsigned long long slot = (unsigned long long)(s_wave + c * 16 + lane);
+                    if (slot < n_live) {
+                        const unsigned s = a.live[slot];
+                        if (s < a.M) a.sigma[s] = sigma[c];   // (a list that keeps its promise never fails this)
+                    }
+                    continue;
+                }
                 const long long s = s_wave + c * 16 + lane;
                 if (s < a.M) a.sigma[s] = sigma[c];
             }
@@ -99,7 +118,18 @@ int nerf_x3s_launch(const NerfArgs& a, hipStream_t st) {
     int cus = 0;
     if (const int rc = cu_count(cus)) return rc;
     const long long n_pass = (a.M + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;
-    nerf_x3s_kernel<<<(unsigned)(n_pass < cus ? n_pass : cus), C::NWAVES * 64, 0, st>>>(a, n_pass);
+    nerf_x3s_kernel<IN_RAYS><<<(unsigned)(n_pass < cus ? n_pass : cus), C::NWAVES * 64, 0, st>>>(a, n_pass);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+// the list's length is on the device: one workgroup per CU (never more than the dense plane has passes), each reads it
+int nerf_x3s_list_launch(const NerfArgs& a, hipStream_t st) {
+    using C = CfgX3s;
+    int cus = 0;
+    if (const int rc = cu_count(cus)) return rc;
+    const long long n_pass = (a.M + C::SAMPLES_PER_WG - 1) / C::SAMPLES_PER_WG;
+    nerf_x3s_kernel<IN_LIST><<<(unsigned)(n_pass < cus ? n_pass : cus), C::NWAVES * 64, 0, st>>>(a, 0);
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;
 }

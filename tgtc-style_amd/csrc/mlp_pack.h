@@ -195,6 +195,21 @@ struct tgtc_style_mx {
     size_t exp_off = 0;      // the row-exponent table behind the streams
 };
 
+// What a NeRF handle in fp16x3 or fp16mx keeps for its density screen (tgtc_net_enable_screen, mlp_nerf.hip; render.hip,
+// the screened passes): the equalised copy of the 12 linears the handle was packed from, and -- once enabled -- the
+// TGTC_PREC_FP16 form of the same weights in an allocation of its own ([bias table][fp16 stream][one ring of slack], what
+// tgtc_nerf_create packs for that precision), the calibrated margin, the policy and its pinned word: every chain render
+// with this handle in a pass that can be screened ends in an asynchronous copy of (candidate count, samples of the pass).
+// Nothing inside tgtc_net::dev moves.
+struct tgtc_screen_state {
+    tgtc::EqualisedNet eq;
+    char* dev = nullptr;                   // nullptr: not enabled
+    float margin = -1.0f;                  // 8 x the calibration's max |sigma_screen - sigma_exact|
+    int mode = 0;                          // TGTC_SCREEN_*
+    volatile uint64_t* landed = nullptr;   // pinned: low word the candidate count, high word the sample count; 0 = nothing yet
+    long long screened = 0, dense = 0;     // chain renders whose pass with this handle was screened / was not
+};
+
 // The opaque handle of the C ABI.
 struct tgtc_net {
     int kind;        // 0 = NeRF (StyleNerf), 1 = style pair (concat MLP + style MLP)
@@ -220,4 +235,5 @@ struct tgtc_net {
     char* stash;
     size_t stash_stride;    // bytes between the regions
     unsigned stash_cap;     // slots per region
+    tgtc_screen_state* screen;   // NeRF handles in fp16x3 / fp16mx only (tgtc_nerf_create)
 };

@@ -454,8 +454,14 @@ constexpr int kCompactParts = 1024;
 constexpr int kCompactBlock = 256;
 constexpr int kCompactCountWord = 64;
 
-__device__ __forceinline__ bool is_live(float w, float min_weight) { return w > min_weight; }   // false for NaN
+// CAND (the candidates of a density screen, render.hip): every sample that is NOT <= min_weight -- NaN included
+template <bool CAND>
+__device__ __forceinline__ bool is_live(float w, float min_weight) {
+    if constexpr (CAND) return !(w <= min_weight);
+    return w > min_weight;   // false for NaN
+}
 
+template <bool CAND>
 __global__ void __launch_bounds__(kCompactBlock) compact_count_kernel(const float* __restrict__ w, unsigned M, unsigned span,
                                                                       float min_weight, unsigned* __restrict__ scratch) {
     __shared__ unsigned wave_n[kCompactBlock / 64];
@@ -463,7 +469,7 @@ __global__ void __launch_bounds__(kCompactBlock) compact_count_kernel(const floa
     const unsigned lo = b0 < M ? (unsigned)b0 : M;
     const unsigned hi = b0 + span < M ? (unsigned)(b0 + span) : M;
     unsigned cnt = 0;
-    for (unsigned s = lo + threadIdx.x; s < hi; s += kCompactBlock) cnt += is_live(w[s], min_weight) ? 1u : 0u;
+    for (unsigned s = lo + threadIdx.x; s < hi; s += kCompactBlock) cnt += is_live<CAND>(w[s], min_weight) ? 1u : 0u;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
     if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = cnt;
@@ -476,6 +482,7 @@ __global__ void __launch_bounds__(kCompactBlock) compact_count_kernel(const floa
     }
 }
 
+template <bool CAND>
 __global__ void __launch_bounds__(kCompactBlock) compact_write_kernel(const float* __restrict__ w, unsigned M, unsigned span,
                                                                       float min_weight, const unsigned* __restrict__ counts,
                                                                       unsigned* __restrict__ live, unsigned* __restrict__ n_live,
@@ -516,7 +523,7 @@ __global__ void __launch_bounds__(kCompactBlock) compact_write_kernel(const floa
     int it = 0;
     for (unsigned s0 = lo; s0 < hi; s0 += kCompactBlock, ++it) {
         const unsigned s = s0 + threadIdx.x;
-        const bool keep = s < hi && is_live(w[s], min_weight);
+        const bool keep = s < hi && is_live<CAND>(w[s], min_weight);
         const unsigned long long m = __ballot(keep);
         if (lane == 0) wave_n[it & 1][wave] = (unsigned)__popcll(m);
         __syncthreads();   // the buffer written two steps ago is free: every wave has passed the barrier in between
@@ -532,17 +539,35 @@ __global__ void __launch_bounds__(kCompactBlock) compact_write_kernel(const floa
     }
 }
 
-int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
-                        hipStream_t st) {
+template <bool CAND>
+static int compact_launches(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
+                            hipStream_t st) {
     // span: a multiple of the block size with kCompactParts * span >= M
     const int64_t per = (M + kCompactParts - 1) / kCompactParts;
     const unsigned span = (unsigned)((per + kCompactBlock - 1) / kCompactBlock * kCompactBlock);
-    compact_count_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch);
+    compact_count_kernel<CAND><<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch);
     TGTC_LAUNCH_CHECK();
-    compact_write_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch + kCompactCountWord,
-                                                                  live, scratch, live_count);
+    if (!live) return TGTC_OK;   // pass 1 alone: the counts of a statistic
+    compact_write_kernel<CAND><<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch + kCompactCountWord,
+                                                                        live, scratch, live_count);
     TGTC_LAUNCH_CHECK();
     return TGTC_OK;
+}
+
+int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* live, uint32_t* scratch, uint32_t* live_count,
+                        hipStream_t st) {
+    return compact_launches<false>(w, M, min_weight, live, scratch, live_count, st);
+}
+
+// The candidates of a density screen: the ascending list of the samples whose screen density is not <= -margin (NaN and
+// +inf are candidates), same scratch layout, same statistic words.
+int launch_compact_candidates(const float* sigma, int64_t M, float margin, uint32_t* live, uint32_t* scratch, hipStream_t st) {
+    return compact_launches<true>(sigma, M, -margin, live, scratch, nullptr, st);
+}
+
+// pass 1 of that alone (the candidate share of a pass that ran dense)
+int launch_count_candidates(const float* sigma, int64_t M, float margin, uint32_t* scratch, hipStream_t st) {
+    return compact_launches<true>(sigma, M, -margin, nullptr, scratch, nullptr, st);
 }
 
 static_assert((kCompactCountWord + kCompactParts) * sizeof(uint32_t) <= kSparseScratchBytes, "counts must fit the scratch");
@@ -571,11 +596,7 @@ __global__ void __launch_bounds__(kCompactBlock) compact_stat_kernel(const unsig
 }
 
 int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scratch, hipStream_t st) {
-    const int64_t per = (M + kCompactParts - 1) / kCompactParts;
-    const unsigned span = (unsigned)((per + kCompactBlock - 1) / kCompactBlock * kCompactBlock);
-    compact_count_kernel<<<kCompactParts, kCompactBlock, 0, st>>>(w, (unsigned)M, span, min_weight, scratch);
-    TGTC_LAUNCH_CHECK();
-    return TGTC_OK;
+    return compact_launches<false>(w, M, min_weight, nullptr, scratch, nullptr, st);
 }
 
 int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st) {

@@ -38,7 +38,13 @@ int launch_compact_live(const float* w, int64_t M, float min_weight, uint32_t* l
 int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scratch, hipStream_t st);
 int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st);
 int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
-                           const uint32_t* live, const uint32_t* n_live, float* rgb, hipStream_t st);
+                           const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st);
+int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                         const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st);
+int nerf_screen_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                          float* sigma, hipStream_t st);
+int launch_compact_candidates(const float* sigma, int64_t M, float margin, uint32_t* live, uint32_t* scratch, hipStream_t st);
+int launch_count_candidates(const float* sigma, int64_t M, float margin, uint32_t* scratch, hipStream_t st);
 int nerf_stash_fill_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                          float* sigma, uint32_t* scratch, uint32_t* ovf, hipStream_t st);
 int nerf_stash_heads_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, int64_t R, int N, uint32_t* scratch,
@@ -317,6 +323,92 @@ static bool cull_wanted(const tgtc_cull_state* c) {
     return total != 0 && live <= total && (double)live < (double)kCullLiveThreshold * (double)total;
 }
 
+// ---- the density screen of the two passes of the plain chain
+// All a frame takes from a density is relu(sigma): a sample with sigma <= 0 has alpha 0 and weight +0 exactly, in the coarse
+// weights that feed the inverse CDF as in the fine composite, so for such a sample only the sign of sigma matters.  A handle
+// with a screen (tgtc_net_enable_screen) carries its weights in fp16 as well, and a margin m that bounds
+// |sigma_screen - sigma_exact| with a factor to spare.  A screened pass is: the fp16 sigma-only launch over all samples, the
+// compaction of the CANDIDATES (screen density not <= -m; NaN is one), the pass's exact kernel over that list alone.  A
+// sample the list leaves out has sigma_exact < sigma_screen + m <= 0: its plane entry (the screen's value) and its exact
+// density have the same relu(), and the frame has the bits of the dense pass.
+// With candidate share C, p the screen launch, c the pass's dense exact launch and l the list launch per listed sample times
+// the samples of the pass: p + C l + launches against c (coarse; l = 1.03 c), against today's fine pass F (fine; l the FULL
+// list launch, density and colour) -- a gain while C < C*.  Measured on the MI355X (tools/time_density_screen.py --step0,
+// profiles/density_screen_timing.json) on the depths of a real 400 x 400 render at 128 + 64:
+//   coarse: p = 14.42 ms, c = 41.20 ms, the list launch 2.059 ns per listed sample (l = 42.18 ms): C* = (c - p) / l = 0.635
+//           (1 - p / c = 0.650).  The candidate share over the benchmark's orbit (spiral_pose 0 .. 119) is 0.261 .. 0.337:
+//           its whole spread, 0.076, lets the statistic come from ANY frame of the orbit; the two compaction kernels, the
+//           statistic's kernel and copy cost 0.2 ms of l, 0.005.  0.635 - 0.076 - 0.005 = 0.55.
+//   fine:   p = 21.66 ms, F = 47.17 ms (the stashed two-phase pass with its compositor), the full list launch 1.819 ns per
+//           listed sample (l = 55.87 ms): C* = (F - p) / l = 0.457.  Candidate share over the orbit 0.112 .. 0.142, spread
+//           0.030; the extra launches (compaction, two statistics) 0.3 ms of l, 0.005.  0.457 - 0.030 - 0.005 = 0.42.
+// Both thresholds clear the orbit's shares (0.337 and 0.142) by a wide margin: AUTO screens both passes of the benchmark's
+// frames once a share has landed.
+constexpr float kScreenCoarseThreshold = 0.55f;
+constexpr float kScreenFineThreshold = 0.42f;
+
+static bool screen_enabled(const tgtc_net* net) { return net->screen && net->screen->dev && net->screen->landed; }
+
+// Does a list of up to M sample indices and the compaction's scratch fit `bytes` of dead planes?
+extern "C" int tgtc_screen_list_fits(size_t bytes, int64_t M) {
+    return M >= 0 && M < ((int64_t)1 << 31) && bytes >= (size_t)M * 4 + kSparseScratchBytes;
+}
+
+// AUTO's rule, pure host code: screen iff a share has landed and lies below the threshold of the pass (0: coarse, 1: fine)
+extern "C" int tgtc_screen_auto_decision(int pass, uint32_t candidates, uint32_t total) {
+    const float thr = pass == 0 ? kScreenCoarseThreshold : kScreenFineThreshold;
+    return total != 0 && candidates <= total && (double)candidates < (double)thr * (double)total;
+}
+
+static bool screen_wanted(const tgtc_screen_state* s, int pass) {
+    if (s->mode != TGTC_SCREEN_AUTO) return s->mode == TGTC_SCREEN_ON;
+    const uint64_t word = *s->landed;   // read without waiting, as cull_wanted reads its word
+    return tgtc_screen_auto_decision(pass, (uint32_t)word, (uint32_t)(word >> 32));
+}
+
+// (count, M) of the counts in `scratch` -> a handle's pinned word, asynchronously; the next render's AUTO reads what landed
+static int land_share(uint32_t* scratch, int64_t M, volatile uint64_t* landed, hipStream_t st) {
+    const uint32_t* stat = nullptr;
+    const int rc = launch_live_stat(scratch, M, &stat, st);
+    if (rc) return rc;
+    TGTC_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(landed), stat, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    return TGTC_OK;
+}
+
+// The coarse pass of a plain chain render that wants no coarse image: sigma_c alone.  Screened where the coarse handle (fp16x3)
+// has a screen and its policy says so: the list and the 8 KiB of scratch live in the fine colour plane, which nothing uses
+// before the fine pass; where they do not fit, the pass is dense.
+static int coarse_sigma_pass(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int nc,
+                             const RenderWorkspace& ws, size_t rgb_f_bytes, hipStream_t st) {
+    const int64_t M = R * (int64_t)nc;
+    tgtc_screen_state* const sc = coarse->precision == TGTC_PREC_FP16X3 && screen_enabled(coarse) ? coarse->screen : nullptr;
+    char* const spare = reinterpret_cast<char*>(ws.rgb_f);
+    if (sc && tgtc_screen_list_fits(rgb_f_bytes, M) && screen_wanted(sc, 0)) {
+        uint32_t* const live = reinterpret_cast<uint32_t*>(spare);
+        uint32_t* const scratch = reinterpret_cast<uint32_t*>(spare + (size_t)M * 4);
+        int rc = nerf_screen_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, nc, ws.sigma_c, st);
+        if (rc) return rc;
+        rc = launch_compact_candidates(ws.sigma_c, M, sc->margin, live, scratch, st);
+        if (rc) return rc;
+        rc = nerf_sigma_list_impl(coarse, rays_o, rays_d, ws.ts_c, R, nc, live, scratch, ws.sigma_c, st);
+        if (rc) return rc;
+        ++sc->screened;
+        return land_share(scratch, M, sc->landed, st);
+    }
+    int rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, nc, nullptr, ws.sigma_c, st);
+    if (rc) return rc;
+    if (sc) {
+        ++sc->dense;
+        if (sc->mode != TGTC_SCREEN_OFF && M < ((int64_t)1 << 31) && rgb_f_bytes >= kSparseScratchBytes) {
+            uint32_t* const scratch = reinterpret_cast<uint32_t*>(spare);
+            rc = launch_count_candidates(ws.sigma_c, M, sc->margin, scratch, st);
+            if (rc) return rc;
+            return land_share(scratch, M, sc->landed, st);
+        }
+    }
+    return TGTC_OK;
+}
+
 // The fine pass and the fine image of the plain chain.  The list and the compaction's scratch live in the planes that are
 // dead once the fine depths exist (ts_c, sigma_c, rgb_c, w_c: contiguous, and the coarse image has been composited): the
 // workspace does not grow.  Where they do not fit, or the samples cannot be indexed by 32 bits, the pass is dense.
@@ -327,10 +419,27 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
     const size_t dead_bytes = (size_t)(reinterpret_cast<char*>(ws.ts_f) - dead);
     tgtc_cull_state* const c = fine->cull;
     const bool listable = c && fine->precision == TGTC_PREC_FP16_FP6 && M < ((int64_t)1 << 31);
-    const bool cull = listable && dead_bytes >= (size_t)M * 4 + kSparseScratchBytes && cull_wanted(c);
+    const bool fits = listable && tgtc_screen_list_fits(dead_bytes, M);
+    // the screen belongs to the two-phase family: TGTC_CULL_OFF switches it off with the rest
+    tgtc_screen_state* const sc = listable && c->mode != TGTC_CULL_OFF && screen_enabled(fine) ? fine->screen : nullptr;
+    const bool screen = sc && fits && screen_wanted(sc, 1);
+    const bool cull = screen || (fits && cull_wanted(c));
     uint32_t* scratch = nullptr;
     int rc;
-    if (cull && fine->stash) {
+    if (screen) {
+        // the screened form: fp16 densities of all samples, the candidates' list, density AND colour of the candidates from
+        // the full list launch; a sample the list leaves out keeps its screen density, which is <= -margin < 0 as its exact
+        // one is below 0: relu() of either is the same +0
+        uint32_t* const live = reinterpret_cast<uint32_t*>(dead);
+        scratch = reinterpret_cast<uint32_t*>(dead + (size_t)M * 4);
+        rc = nerf_screen_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ws.sigma_f, st);
+        if (rc) return rc;
+        rc = launch_compact_candidates(ws.sigma_f, M, sc->margin, live, scratch, st);
+        if (rc) return rc;
+        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, ws.sigma_f, st);
+        if (rc) return rc;
+        ++c->culled, ++sc->screened;
+    } else if (cull && fine->stash) {
         // the stashed form (mlp_nerf_mx2_stash.hip): the density launch parks layer 7's output of its live samples, the
         // heads-only launch reads it back; live samples that found their wave's region full are the list of the list launch
         // (which runs its prologue alone when there are none).  The per-wave counts are the statistic's parts.
@@ -340,7 +449,7 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         if (rc) return rc;
         rc = nerf_stash_heads_impl(fine, rays_o, rays_d, R, nt, scratch, ws.rgb_f, st);
         if (rc) return rc;
-        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ovf, scratch, ws.rgb_f, st);
+        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, ovf, scratch, ws.rgb_f, nullptr, st);
         if (rc) return rc;
         ++c->culled;
     } else if (cull) {
@@ -350,7 +459,7 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         if (rc) return rc;
         rc = launch_compact_live(ws.sigma_f, M, 0.0f, live, scratch, nullptr, st);
         if (rc) return rc;
-        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, st);
+        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, nullptr, st);
         if (rc) return rc;
         ++c->culled;
     } else {
@@ -369,12 +478,28 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
     rc = cull ? launch_composite_live_colours(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st)
               : launch_composite(ws.rgb_f, ws.sigma_f, ws.ts_f, R, nt, rgb_fine, t_fine, nullptr, st);
     if (rc) return rc;
+    if (screen) {
+        // the scratch holds the candidates' counts: they land first, then the live statistic is taken as the dense pass
+        // takes it (sigma_f > 0 holds for the same samples as in a dense plane), in the same scratch
+        rc = land_share(scratch, M, sc->landed, st);
+        if (rc) return rc;
+        rc = launch_count_live(ws.sigma_f, M, 0.0f, scratch, st);
+        if (rc) return rc;
+    }
     if (scratch) {
         // (live count, M) -> the handle's pinned word, asynchronously; the next render's AUTO reads whatever has landed
-        const uint32_t* stat = nullptr;
-        rc = launch_live_stat(scratch, M, &stat, st);
+        rc = land_share(scratch, M, c->landed, st);
         if (rc) return rc;
-        TGTC_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t*>(c->landed), stat, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (sc && !screen) {
+        // the candidate share of a pass that was not screened: the count kernel at -margin over the exact densities
+        if (scratch) {
+            rc = launch_count_candidates(ws.sigma_f, M, sc->margin, scratch, st);
+            if (rc) return rc;
+            rc = land_share(scratch, M, sc->landed, st);
+            if (rc) return rc;
+        }
+        ++sc->dense;
     }
     return TGTC_OK;
 }
@@ -405,7 +530,8 @@ extern "C" int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fi
     if (rc) return rc;
     // coarse pass: only the weights are consumed unless the caller asks for the coarse image
     float* rgb_c = rgb_coarse ? ws.rgb_c : nullptr;
-    rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, rgb_c, ws.sigma_c, st);
+    if (rgb_coarse || t_coarse) rc = nerf_forward_rays_impl(coarse, rays_o, rays_d, ws.ts_c, R, n_coarse, rgb_c, ws.sigma_c, st);
+    else rc = coarse_sigma_pass(coarse, rays_o, rays_d, R, n_coarse, ws, (size_t)R * (n_coarse + n_fine) * 3 * sizeof(float), st);
     if (rc) return rc;
     rc = coarse_to_fine(rgb_c, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, rgb_coarse, t_coarse, ws.ts_f, st);
     if (rc) return rc;

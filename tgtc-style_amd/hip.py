@@ -26,6 +26,10 @@ CULL_AUTO = 0         # tgtc_net_set_cull: two-phase fine pass iff the last land
 CULL_OFF = 1          # always the dense fine pass
 CULL_ON = 2           # always densities first, the colour head on the live samples only
 
+SCREEN_AUTO = 0       # tgtc_net_set_screen: screened pass iff the last landed candidate share is below the pass's threshold
+SCREEN_OFF = 1        # never
+SCREEN_ON = 2         # wherever the list fits
+
 _lib = None
 
 c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
@@ -65,6 +69,17 @@ _SIGNATURES = {
     "tgtc_net_set_stash": [c_void_p, c_void_p, c_size_t],
     "tgtc_nerf_stash_fill": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_stash_heads": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
+    "tgtc_net_enable_screen": [c_void_p, c_void_p],
+    "tgtc_net_screen_margin": [c_void_p],
+    "tgtc_net_set_screen": [c_void_p, c_int],
+    "tgtc_net_screen_fraction": [c_void_p],
+    "tgtc_net_screened_renders": [c_void_p],
+    "tgtc_screen_list_fits": [c_size_t, c_int64],
+    "tgtc_screen_auto_decision": [c_int, ctypes.c_uint32, ctypes.c_uint32],
+    "tgtc_nerf_screen_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p],
+    "tgtc_nerf_sigma_list": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_nerf_forward_list_sigma": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p],
     "tgtc_composite": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_train": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
@@ -83,7 +98,8 @@ _SIGNATURES = {
                              c_void_p, c_void_p],
     "tgtc_latents_backward": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p],
 }
-_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_live_fraction": c_float, "tgtc_net_stash_bytes": c_size_t, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
+_RESTYPES = {"tgtc_last_error": ctypes.c_char_p, "tgtc_net_screen_margin": c_float, "tgtc_net_screen_fraction": c_float,
+             "tgtc_net_screened_renders": ctypes.c_longlong, "tgtc_net_live_fraction": c_float, "tgtc_net_stash_bytes": c_size_t, "tgtc_net_culled_renders": ctypes.c_longlong, "tgtc_render_workspace_bytes": c_size_t,
              "tgtc_render_styled_multi_workspace_bytes": c_size_t,
              "tgtc_render_styled_sparse_workspace_bytes": c_size_t,
              "tgtc_geometry_cache_bytes": c_size_t, "tgtc_restyle_workspace_bytes": c_size_t,
@@ -231,6 +247,7 @@ class Net:
         self.handle = handle
         self.precision = precision
         self.stash = None
+        self.screen_tried = False   # enable_screen has run (whether or not the calibration left a screen)
 
     def set_cull(self, mode):
         """The policy of the two-phase fine pass for chain renders with this net as the fine network (CULL_*)."""
@@ -253,6 +270,29 @@ class Net:
             require_gpu(buf)
             check(load().tgtc_net_set_stash(self.handle, ptr(buf), buf.numel() * buf.element_size()))
         self.stash = buf
+
+    def enable_screen(self):
+        """Pack the fp16 form of an fp16x3 / fp16mx NeRF handle and calibrate its margin (tgtc_net_enable_screen: once, one
+        host synchronisation; RuntimeError for a style or fp16 handle).  The margin stays -1 where the calibration finds no
+        error to scale (a constant density): the handle then renders as before."""
+        check(load().tgtc_net_enable_screen(self.handle, stream()))
+        self.screen_tried = True
+
+    def set_screen(self, mode):
+        """The policy of the screened passes of chain renders with this net (SCREEN_*)."""
+        check(load().tgtc_net_set_screen(self.handle, mode))
+
+    def screen_margin(self):
+        """The calibrated margin of the density screen; -1.0 when no screen is enabled."""
+        return float(load().tgtc_net_screen_margin(self.handle))
+
+    def screen_fraction(self):
+        """Share of candidates (screen density not <= -margin) in the last such pass whose statistic has landed; -1.0 while unknown."""
+        return float(load().tgtc_net_screen_fraction(self.handle))
+
+    def screened_renders(self):
+        """How many chain renders screened their pass with this net."""
+        return int(load().tgtc_net_screened_renders(self.handle))
 
     def has_mx(self):
         """Whether this style pair carries its fp16mx streams (tgtc_style_enable_mx)."""

@@ -139,7 +139,9 @@ class RayRenderer:
 
     _CULL = {None: hip.CULL_AUTO, False: hip.CULL_OFF, True: hip.CULL_ON}
 
-    def __init__(self, coarse, fine, style=None, fused=True, cull=None, stash=None):
+    _SCREEN = {None: hip.SCREEN_AUTO, False: hip.SCREEN_OFF, True: hip.SCREEN_ON}
+
+    def __init__(self, coarse, fine, style=None, fused=True, cull=None, stash=None, screen=None):
         """fused=True: the library's fastest path (TGTC_PATH_AUTO) -- a single persistent ray kernel where one is built, except
         for coarse fp16x3 + fine fp16mx, whose fine pass runs faster on the two-tile per-sample kernel (the split path).
         fused="single" asks for the single ray kernel and nothing else (TGTC_PATH_RAY_KERNEL).  fused=False forces the chain
@@ -152,7 +154,17 @@ class RayRenderer:
         stash (the same renders): None attaches the stash of the two-phase pass as STASH_DEFAULT says, True / False force it,
         a uint8 device tensor is attached as it is (any size from one slot per region up is correct);
         it is allocated at the first such render, STASH_SHARE x 932 bytes per fine sample (about 4 GB for 400 x 400 rays at
-        128 + 64), and never with cull=False.  The same bits again."""
+        128 + 64), and never with cull=False.  The same bits again.
+        screen (plain render on the chain; coarse fp16x3, fine fp16mx): the density screen of the two passes (include/tgtc_hip.h)
+        -- fp16 densities of all samples first, the exact kernels on the candidates only.  None enables the screen on both
+        handles at the first such render (one host synchronisation per handle) and leaves the decision to the library
+        (TGTC_SCREEN_AUTO), True forces it wherever it fits, False switches it off; one value for both passes, or a pair
+        (coarse, fine).  cull=False switches the fine screen off as well.  The same bits again."""
+        if isinstance(screen, tuple):
+            if len(screen) != 2 or any(v not in self._SCREEN for v in screen):
+                raise ValueError("screen must be None, True, False or a pair of those (coarse, fine)")
+        elif screen not in self._SCREEN:
+            raise ValueError("screen must be None, True, False or a pair of those (coarse, fine)")
         if not (stash is None or stash is True or stash is False or isinstance(stash, torch.Tensor)):
             raise ValueError("stash must be None, True, False or a uint8 device tensor")
         if fused not in (True, False, "single"):
@@ -161,6 +173,7 @@ class RayRenderer:
             raise ValueError("cull must be None, True or False")
         self.coarse, self.fine, self.style, self.fused, self.cull = coarse, fine, style, fused, cull
         self.stash = stash
+        self.screen = screen
         self._stash = None
         self._ws = None
         self._ws_multi = None
@@ -169,6 +182,17 @@ class RayRenderer:
     def apply_cull(self):
         """Put this renderer's `cull` on the fine handle (a host call; handles are repacked when weights change)."""
         self.fine.packed().set_cull(self._CULL[self.cull])
+
+    def apply_screen(self):
+        """Put this renderer's `screen` on the two handles, enabling the screen where a pass may be screened (host calls;
+        handles are repacked when weights change).  Handles in fp16 have no screen."""
+        pair = self.screen if isinstance(self.screen, tuple) else (self.screen, self.screen)
+        for net, want, prec in ((self.coarse.packed(), pair[0], "fp16x3"), (self.fine.packed(), pair[1], "fp16mx")):
+            if net.precision != prec:
+                continue
+            if want is not False and not net.screen_tried:
+                net.enable_screen()
+            net.set_screen(self._SCREEN[want])
 
     # The live share the lazily attached stash is sized for: the library's kCullLiveThreshold (csrc/render.hip).  AUTO never
     # culls above it, so a frame AUTO culls overflows only where single waves see more live samples than the frame's share.
@@ -297,6 +321,7 @@ class RayRenderer:
             self.apply_cull()
             if path == hip.PATH_CHAIN:
                 self._apply_stash(R, n_coarse + n_fine, dev)
+                self.apply_screen()
             hip.check(lib.tgtc_render_rays_plain(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o),
                                                  hip.ptr(rays_d), R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
                                                  *rest))

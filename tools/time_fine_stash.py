@@ -50,7 +50,7 @@ def main():
 
     if not args.all_live:
         # the fine depths and the list of a real frame
-        r = rendering.RayRenderer(coarse, fine, fused=False, cull=False)
+        r = rendering.RayRenderer(coarse, fine, fused=False, cull=False, screen=False)
         o, d = (x.contiguous() for x in utils.gen_rays(H, W, focal, synth.spiral_pose(0)))
         r.render(o, d, NC, NF, near=0., far=1.)
         torch.cuda.synchronize()
@@ -83,12 +83,12 @@ def main():
         net.set_stash(None)
 
     rays = [utils.gen_rays(H, W, focal, synth.spiral_pose(i)) for i in range(2)]
-    renderers = {"OFF": rendering.RayRenderer(coarse, fine, fused=False, cull=False),
-                 "ON_no_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=True, stash=False),
-                 "ON_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=True, stash=stash),
-                 "AUTO_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=None, stash=stash)}
+    renderers = {"OFF": rendering.RayRenderer(coarse, fine, fused=False, cull=False, screen=False),
+                 "ON_no_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=True, stash=False, screen=False),
+                 "ON_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=True, stash=stash, screen=False),
+                 "AUTO_stash": rendering.RayRenderer(coarse, fine, fused=False, cull=None, stash=stash, screen=False)}
     if args.all_live:      # culling can only lose here: time what the default does against OFF, and OFF against itself
-        renderers = {"OFF": renderers["OFF"], "OFF_again": rendering.RayRenderer(coarse, fine, fused=False, cull=False),
+        renderers = {"OFF": renderers["OFF"], "OFF_again": rendering.RayRenderer(coarse, fine, fused=False, cull=False, screen=False),
                      "AUTO_stash": renderers["AUTO_stash"]}
 
     def call(mode, i=[0]):

@@ -52,7 +52,7 @@ def main():
         libs[tag] = bind(path)
     coarse, fine = bench.build_nets("fp16x3+fp16mx")
     R = H * W
-    r = rendering.RayRenderer(coarse, fine, fused=False, cull=False)
+    r = rendering.RayRenderer(coarse, fine, fused=False, cull=False, screen=False)
     o, d = (x.contiguous() for x in utils.gen_rays(H, W, synth.fern_intrinsics(H, W), synth.spiral_pose(0)))
     r.render(o, d, NC, NF, near=0., far=1.)
     torch.cuda.synchronize()

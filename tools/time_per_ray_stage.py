@@ -31,7 +31,7 @@ def main():
     coarse, fine = bench.build_nets("fp16x3+fp16mx")
     R = H * W
     # the planes of a real frame: a dense render leaves all of them in the workspace (csrc/render.hip, RenderWorkspace)
-    r = rendering.RayRenderer(coarse, fine, fused=False, cull=False)
+    r = rendering.RayRenderer(coarse, fine, fused=False, cull=False, screen=False)
     o, d = (x.contiguous() for x in utils.gen_rays(H, W, synth.fern_intrinsics(H, W), synth.spiral_pose(0)))
     r.render(o, d, NC, NF, near=0., far=1.)
     torch.cuda.synchronize()

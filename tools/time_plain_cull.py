@@ -121,7 +121,7 @@ def main():
             args.poses, shares.min(), shares.mean(), shares.max(), result["live_share_poses"]["max_step_between_consecutive_poses"]), flush=True)
     else:
         rays = [utils.gen_rays(H, W, focal, synth.spiral_pose(i)) for i in range(2)]
-        renderers = {mode: rendering.RayRenderer(coarse, fine, fused=False, cull=cull)
+        renderers = {mode: rendering.RayRenderer(coarse, fine, fused=False, cull=cull, screen=False)
                      for mode, cull in (("OFF", False), ("ON", True), ("AUTO", None))}
         # one handle carries the mode: set it before every call
         def call(mode, i=[0]):
