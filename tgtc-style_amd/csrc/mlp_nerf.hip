@@ -322,14 +322,19 @@ int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double
 }
 
 // The density screen: sigma of every sample from the handle's TGTC_PREC_FP16 form, one MFMA product per
-// weight -- the sigma-only launch an fp16 handle runs (the caller has checked that the screen is enabled)
+// weight (the caller has checked that the screen is enabled).  Its kernel is the four-tile persistent stream of
+// mlp_nerf_fp16s.hip; with TGTC_SCREEN_CFGFAST=1 in the environment (read at every call: the yardstick the stream is held
+// against, in timing and in tests) it is the sigma-only launch an fp16 handle runs.  The densities are the same bits either
+// way, but for samples whose position is not finite: the stream gives them NaN, the fp16 ReLU of CfgFast a finite density.
 int nerf_screen_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                           float* sigma, hipStream_t st) {
     NerfArgs a{};
     a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.sigma = sigma;
     a.bias = net->screen->dev;
     a.stream = net->screen->dev + kNerfBiasBytes;
-    return launch_nerf<CfgFast, IN_RAYS, false>(a, st);
+    const char* e = std::getenv("TGTC_SCREEN_CFGFAST");
+    if (e && e[0] == '1') return launch_nerf<CfgFast, IN_RAYS, false>(a, st);
+    return nerf_fp16s_launch(a, st);
 }
 
 // ---- the stashed two-phase fine pass (mlp_nerf_mx2_stash.hip).  scratch: kSparseScratchBytes laid out as the compaction's

@@ -40,5 +40,8 @@ int nerf_mx2_heads_launch(const NerfArgs& a, const NerfStashArgs& s, hipStream_t
 int nerf_x3s_launch(const NerfArgs& a, hipStream_t st);
 // the same over a device-side list (a.live, a.n_live): sigma[live[slot]], nothing else
 int nerf_x3s_list_launch(const NerfArgs& a, hipStream_t st);
+// fp16 (one product), rays in, sigma out (the density screen): four column tiles per wave, one wave per SIMD, persistent
+// (mlp_nerf_fp16s.hip); a.bias / a.stream are a handle's TGTC_PREC_FP16 form
+int nerf_fp16s_launch(const NerfArgs& a, hipStream_t st);
 
 }  // namespace tgtc

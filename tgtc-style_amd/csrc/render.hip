@@ -334,18 +334,21 @@ static bool cull_wanted(const tgtc_cull_state* c) {
 // With candidate share C, p the screen launch, c the pass's dense exact launch and l the list launch per listed sample times
 // the samples of the pass: p + C l + launches against c (coarse; l = 1.03 c), against today's fine pass F (fine; l the FULL
 // list launch, density and colour) -- a gain while C < C*.  Measured on the MI355X (tools/time_density_screen.py --step0,
-// profiles/density_screen_timing.json) on the depths of a real 400 x 400 render at 128 + 64:
-//   coarse: p = 14.42 ms, c = 41.20 ms, the list launch 2.059 ns per listed sample (l = 42.18 ms): C* = (c - p) / l = 0.635
-//           (1 - p / c = 0.650).  The candidate share over the benchmark's orbit (spiral_pose 0 .. 119) is 0.261 .. 0.337:
+// profiles/screen_stream_timing.json "step0"; the screen launch is the four-tile stream of mlp_nerf_fp16s.hip) on the depths
+// of a real 400 x 400 render at 128 + 64:
+//   coarse: p = 12.77 ms, c = 38.42 ms, the list launch 1.932 ns per listed sample (l = 39.57 ms): C* = (c - p) / l = 0.648
+//           (1 - p / c = 0.668).  The candidate share over the benchmark's orbit (spiral_pose 0 .. 119) is 0.261 .. 0.337:
 //           its whole spread, 0.076, lets the statistic come from ANY frame of the orbit; the two compaction kernels, the
-//           statistic's kernel and copy cost 0.2 ms of l, 0.005.  0.635 - 0.076 - 0.005 = 0.55.
-//   fine:   p = 21.66 ms, F = 47.17 ms (the stashed two-phase pass with its compositor), the full list launch 1.819 ns per
-//           listed sample (l = 55.87 ms): C* = (F - p) / l = 0.457.  Candidate share over the orbit 0.112 .. 0.142, spread
-//           0.030; the extra launches (compaction, two statistics) 0.3 ms of l, 0.005.  0.457 - 0.030 - 0.005 = 0.42.
+//           statistic's kernel and copy cost 0.2 ms of l, 0.005.  0.648 - 0.076 - 0.005 = 0.56.
+//   fine:   p = 19.12 ms, F = 44.35 ms (the stashed two-phase pass with its compositor), the full list launch 1.689 ns per
+//           listed sample (l = 51.87 ms): C* = (F - p) / l = 0.486.  Candidate share over the orbit 0.112 .. 0.142, spread
+//           0.030; the extra launches (compaction, two statistics) 0.3 ms of l, 0.005.  0.486 - 0.030 - 0.005 = 0.45.
+// (With the CfgFast screen launch of profiles/density_screen_timing.json, on a slower device: p = 14.42 of c = 41.20 and
+// 21.66 of F = 47.17 ms, thresholds 0.55 and 0.42.)
 // Both thresholds clear the orbit's shares (0.337 and 0.142) by a wide margin: AUTO screens both passes of the benchmark's
 // frames once a share has landed.
-constexpr float kScreenCoarseThreshold = 0.55f;
-constexpr float kScreenFineThreshold = 0.42f;
+constexpr float kScreenCoarseThreshold = 0.56f;
+constexpr float kScreenFineThreshold = 0.45f;
 
 static bool screen_enabled(const tgtc_net* net) { return net->screen && net->screen->dev && net->screen->landed; }
 
