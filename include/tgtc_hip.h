@@ -262,6 +262,14 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  * samples; the compaction of the candidates (screen density not <= -m; NaN and +inf are candidates) into an ascending
  * device-side list; the pass's exact kernel over that list alone.  While |sigma_screen - sigma_exact| < m every sample the
  * list leaves out has sigma_exact < 0, and the frame has the BITS of the dense pass.
+ * THE DOMAIN RULE.  The screen decides only inside its declared box |x|, |y|, |z| <= 2 (sample position o + t d in float64; a
+ *   coordinate exactly +-2 is inside).  A sample with a coordinate outside it, or not finite, gets NaN from the screen launch
+ *   and so is ALWAYS a candidate: the exact kernel computes it, as in a dense pass -- the bits hold there by construction,
+ *   whatever near / far and whatever the scene's scale.  Inside the box they rest on the margin, which is measured, not
+ *   proven: m is calibrated on rays that fill this box, and tests/test_screen_domain_gpu.py holds the error to m / 2 on it for
+ *   the synthetic nets in four weight families (largest seen: 0.13 m).  NDC frames (|x|, |y| <= 1.3, |z| <= 1) never meet the
+ *   rule; a scene that lives outside the box renders correctly with every sample a candidate, and AUTO then leaves its
+ *   passes dense.
  *   coarse pass: when no coarse image is asked and the coarse handle (fp16x3) has a screen; the exact densities of the
  *                candidates from tgtc_nerf_sigma_list.  List + scratch live in the fine colour plane (dense where
  *                R x (n_coarse + n_fine) x 12 bytes < R x n_coarse x 4 + 8192).
@@ -271,8 +279,8 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  *                handle switches it off as well.
  * tgtc_render_workspace_bytes is what it was; there is no host synchronisation in a render.
  * tgtc_net_enable_screen(net, stream): packs the fp16 form and calibrates the margin -- screen and exact sigma-only launches
- *   on 256 fixed host-generated rays (origins uniform in [-1.5, 1.5]^2 x {-1}, directions (u, v, 2) with u, v uniform in
- *   [-1, 1]) x 128 depths equally spaced on [0, 1]; m = 8 x max |sigma_screen - sigma_exact|.  ONE host synchronisation, a host
+ *   on 256 fixed host-generated rays (each between two points uniform in the box) x 128 depths equally spaced on [0, 1]: the
+ *   positions fill the box; m = 8 x max |sigma_screen - sigma_exact|.  ONE host synchronisation, a host
  *   call like packing.  Idempotent.  A zero or non-finite calibration error leaves the screen disabled (TGTC_OK; the handle
  *   renders as before).  Style handles and TGTC_PREC_FP16 handles -> TGTC_ERR_UNSUPPORTED; NULL -> TGTC_ERR_ARG.
  * tgtc_net_screen_margin: m, or -1 when no screen is enabled (and for NULL).
@@ -289,7 +297,9 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  * tgtc_screen_list_fits / tgtc_screen_auto_decision: the two rules as pure host functions -- does a list of up to M indices
  *   and the 8192-byte scratch fit `bytes`; does AUTO screen pass 0 (coarse) / 1 (fine) on a landed (candidates, total).
  * The launches as entries of their own (tests, tools):
- *   tgtc_nerf_screen_rays: sigma [R,N] from the screen form (TGTC_ERR_UNSUPPORTED without a screen).
+ *   tgtc_nerf_screen_rays: sigma [R,N] from the screen form (TGTC_ERR_UNSUPPORTED without a screen): NaN for exactly the
+ *     samples outside the box or not finite, and for the others the bits of the sigma-only launch of a TGTC_PREC_FP16 handle
+ *     of the same layers.
  *   tgtc_nerf_sigma_list: sigma[s] of the listed samples, the bits of tgtc_nerf_forward_rays(rgb = NULL), nothing else
  *     touched; TGTC_PREC_FP16X3 handles only (csrc/mlp_nerf_x3s.hip, the IN_LIST instance).  List rules as tgtc_nerf_forward_list.
  *   tgtc_nerf_forward_list_sigma: tgtc_nerf_forward_list that also writes sigma[s] of the listed samples. */

@@ -139,3 +139,20 @@ def test_front_end_takes_free_gaps_one_instruction_each(gens):
         gap = lines[mfma[gp - 1] + 1:mfma[gp]]
         assert not any(ln.startswith(("global_load_lds", "s_barrier", "v_pk_max_f16")) for ln in gap), gp
         assert sum(1 for ln in gap if ln.startswith("v_cvt_pk_f16_f32")) <= (1 if lines[k].startswith("v_cvt_pk_f16_f32") else 0), gp
+
+
+def test_box_test_is_three_compares_per_tile_on_an_inline_constant(gens):
+    """the domain rule of DESIGN 3.1 "The screen's domain": not (|p| <= BOX) per coordinate -- true of a NaN and an infinity too
+    -- by the abs modifier against a float64 inline constant; the serial stream has no front end and no compare"""
+    G, serial, g = gens
+    lines = g.e.lines
+    assert G.BOX == 2.0
+    at = [k for k, ln in enumerate(lines) if ln.startswith("v_cmp_nle_f64")]
+    assert len(at) == 3 * G.NCT and set(at) <= set(g.front_at)
+    for c in range(G.NCT):
+        a, b, d = (lines[k].replace(",", " ").split() for k in at[3 * c:3 * c + 3])
+        assert (a[1], b[1], d[1]) == ("s[90:91]", "s[92:93]", "vcc") and a[3] == b[3] == d[3] == "2.0"
+        regs = [x[2] for x in (a, b, d)]
+        assert all(r.startswith("|v[") and r.endswith("]|") for r in regs) and len(set(regs)) == 3
+    assert not any("v_cmp_class" in ln or "s86" in ln for ln in lines)
+    assert not any(ln.startswith("v_cmp_nle_f64") for ln in serial.e.lines)

@@ -325,7 +325,8 @@ int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double
 // weight (the caller has checked that the screen is enabled).  Its kernel is the four-tile persistent stream of
 // mlp_nerf_fp16s.hip; with TGTC_SCREEN_CFGFAST=1 in the environment (read at every call: the yardstick the stream is held
 // against, in timing and in tests) it is the sigma-only launch an fp16 handle runs.  The densities are the same bits either
-// way, but for samples whose position is not finite: the stream gives them NaN, the fp16 ReLU of CfgFast a finite density.
+// way, but for samples whose position is outside the screen's box |p| <= kScreenBox or not finite: the stream gives them NaN (a
+// candidate of every screened pass), CfgFast the density of its arithmetic, which is finite even for a NaN (the fp16 ReLU).
 int nerf_screen_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                           float* sigma, hipStream_t st) {
     NerfArgs a{};
@@ -501,15 +502,18 @@ extern "C" int tgtc_net_enable_screen(tgtc_net* net, void* stream) {
     DeviceBuf form;
     TGTC_HIP_CHECK(hipMalloc(&form.p, total));
     TGTC_HIP_CHECK(hipMemcpy(form.p, host.data(), total, hipMemcpyHostToDevice));
-    // 2. the calibration: screen and exact densities of 256 fixed rays x 128 depths on [0, 1]
+    // 2. the calibration: screen and exact densities of 256 fixed rays x 128 depths on [0, 1] that fill the screen's box --
+    // every ray runs between two points uniform in it (both 2^-40 relative inside the faces: whatever o + t d rounds to is
+    // inside), so the margin speaks for exactly the positions the screen's kernel accepts (kScreenBox, mlp_nerf_mx.h)
     constexpr int R = kScreenCalRays, N = kScreenCalDepths;
+    constexpr double kHalf = kScreenBox * (1.0 - 0x1p-40);
     std::vector<double> rays(2 * R * 3);
     std::vector<float> ts((size_t)R * N);
     ScreenRng rng{0x7467746373637265ull};
     for (int r = 0; r < R; ++r) {
         double* o = &rays[r * 3], *d = &rays[(R + r) * 3];
-        o[0] = 3.0 * rng.uniform() - 1.5, o[1] = 3.0 * rng.uniform() - 1.5, o[2] = -1.0;
-        d[0] = 2.0 * rng.uniform() - 1.0, d[1] = 2.0 * rng.uniform() - 1.0, d[2] = 2.0;
+        for (int k = 0; k < 3; ++k) o[k] = kHalf * (2.0 * rng.uniform() - 1.0);
+        for (int k = 0; k < 3; ++k) d[k] = kHalf * (2.0 * rng.uniform() - 1.0) - o[k];
         for (int i = 0; i < N; ++i) ts[(size_t)r * N + i] = (float)i / (float)(N - 1);
     }
     DeviceBuf d_rays, d_ts, d_sigma;

@@ -2,7 +2,7 @@
 // weight, on FOUR column tiles per wave, one wave per SIMD: a persistent kernel (one workgroup of four waves per CU, 256 samples
 // per pass, the weight ring never drains between passes) whose pass is ONE generated instruction stream (tools/gen_fp16s_asm.py
 // -> fp16s_asm_nerf.inc).  Same arithmetic per sample, in the same order, as nerf_mlp_kernel<CfgFast, IN_RAYS, false>
-// (mlp_nerf.hip): bit-identical densities wherever the sample's position is finite, a quarter of the weight-side work per MFMA
+// (mlp_nerf.hip): bit-identical densities wherever the sample's position is inside the screen's box, a quarter of the weight-side work per MFMA
 // of a one-tile wave and half of CfgFast's.
 // It reads the screen's packed form as it is: the TGTC_PREC_FP16 fragment stream of 1 KiB fragments and the bias table.
 // The stream of a pass also carries, between its MFMAs, the front end of the wave's next pass (sample loads, float64 positions,
@@ -51,7 +51,8 @@ __device__ __forceinline__ void fp16s_front(const NerfArgs& a, long long s_wave,
     nerf_encode<NCT, false, false>(a, pos, dir, sidx, g, pe_h, pe_l, de_h, de_l);
 #pragma unroll
     for (int c = 0; c < NCT; ++c)
-        if (!(__builtin_isfinite(pos[c][0]) && __builtin_isfinite(pos[c][1]) && __builtin_isfinite(pos[c][2]))) bad |= 1u << c;
+        if (!(__builtin_fabs(pos[c][0]) <= kScreenBox && __builtin_fabs(pos[c][1]) <= kScreenBox && __builtin_fabs(pos[c][2]) <= kScreenBox))
+            bad |= 1u << c;
 #endif
 #pragma unroll
     for (int c = 0; c < NCT; ++c) keep[c][0] = pe_h[0][c], keep[c][1] = pe_h[1][c];
@@ -72,6 +73,7 @@ __global__ void __launch_bounds__(256, 1) nerf_fp16s_kernel(NerfArgs a, long lon
     static_assert(NerfLayout::kFragsSigma == kFp16sFrags && kPad == kFp16sPadChunks && C::RING_BYTES == 131072 && C::FRAG_BYTES == 1024 &&
                       kPiece % 4096 == 0 && kChunk == kChunkBytes,
                   "the generated stream was laid out for this ring");
+    static_assert(kFp16sBox == kScreenBox, "the generated front end tests positions against the HIP front end's box");
     static_assert(!FRONT || IN_MODE == IN_RAYS, "the in-stream front end loads samples of rays");
 
     // ring | biases
@@ -95,9 +97,10 @@ __global__ void __launch_bounds__(256, 1) nerf_fp16s_kernel(NerfArgs a, long lon
         });
     }
 
-    // bit c: the lane's sample of tile c has a position that is not finite.  The ReLU of the fp16 layers (v_pk_max_f16 with
-    // zero) returns zero for a NaN, so such a sample would come out with the finite density of an all-zero layer; it gets NaN
-    // instead, which the screened passes list as a candidate (render.hip) -- as the exact kernels' density of it is.
+    // bit c: the lane's sample of tile c has a position outside the screen's box: a coordinate with not (|p| <= kScreenBox), a
+    // NaN or an infinity included.  The margin is calibrated on the box and says nothing beyond it, and the ReLU of the fp16
+    // layers (v_pk_max_f16 with zero) returns zero for a NaN, the finite density of an all-zero layer; such a sample gets
+    // NaN instead, which the screened passes list as a candidate (render.hip): the exact kernels decide about it.
     unsigned bad = 0;
     half8 keep[NCT][2];
     if constexpr (FRONT) {

@@ -42,6 +42,9 @@ int nerf_x3s_launch(const NerfArgs& a, hipStream_t st);
 int nerf_x3s_list_launch(const NerfArgs& a, hipStream_t st);
 // fp16 (one product), rays in, sigma out (the density screen): four column tiles per wave, one wave per SIMD, persistent
 // (mlp_nerf_fp16s.hip); a.bias / a.stream are a handle's TGTC_PREC_FP16 form
+// The screen's declared domain (DESIGN 3.1 "The screen's domain"): a sample with a coordinate outside |p| <= kScreenBox, or not
+// finite, gets NaN for its density, which the screened passes list as a candidate; the margin is calibrated on this box.
 int nerf_fp16s_launch(const NerfArgs& a, hipStream_t st);
+constexpr double kScreenBox = 2.0;
 
 }  // namespace tgtc

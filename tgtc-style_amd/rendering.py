@@ -159,7 +159,9 @@ class RayRenderer:
         -- fp16 densities of all samples first, the exact kernels on the candidates only.  None enables the screen on both
         handles at the first such render (one host synchronisation per handle) and leaves the decision to the library
         (TGTC_SCREEN_AUTO), True forces it wherever it fits, False switches it off; one value for both passes, or a pair
-        (coarse, fine).  cull=False switches the fine screen off as well.  The same bits again."""
+        (coarse, fine).  cull=False switches the fine screen off as well.  The same bits again: measured for samples inside the
+        screen's box |x|, |y|, |z| <= 2, where its margin is calibrated; a sample outside it is always handed to the exact
+        kernel, so near / far beyond NDC cost time, not bits (DESIGN 3.1 "The screen's domain")."""
         if isinstance(screen, tuple):
             if len(screen) != 2 or any(v not in self._SCREEN for v in screen):
                 raise ValueError("screen must be None, True, False or a pair of those (coarse, fine)")

@@ -67,6 +67,8 @@ FT = LAST_VGPR + 1
 LAST_VGPR_SERIAL, LAST_VGPR = LAST_VGPR, FT + 39
 MIN_LOAD_TO_USE = 256          # MFMAs between a tile's last load and the counted wait in front of its first use (> 2 us)
 FRONT_EVERY = 2                # the front end takes every second free gap: it ends in the pass's last quarter
+BOX = 2.0                      # the screen's declared box |x|, |y|, |z| <= BOX (kScreenBox of csrc/mlp_nerf_mx.h): a sample outside
+assert BOX in (0.5, 1.0, 2.0, 4.0)   # it gets NaN; a float64 inline constant of the compare, no literal and no register
 X, Y = 0, 1                    # the activation sets of nerf_sigma_layers(): X in VGPRs, Y in AGPRs
 
 
@@ -249,8 +251,8 @@ class PassFp16s:
         coordinate (2 g + i) mod 3 -- the lane loads the three coordinates rotated by 2 g mod 3, so that pair i reads
         rotated coordinate i mod 3 in every lane -- at band (8 g + i) / 3, a nibble of a per-lane constant.  Lane group 3
         (rotation 0) replaces pairs 6 and 7 by the raw (x, y), (z, 0).
-        Scalars the stream owns: s[84:85] lanes 48..63, s86 the class mask (NaN or infinity), s87 a literal on its way,
-        s[88:89] kInv2Pi, s[90:93] compare results."""
+        Scalars the stream owns: s[84:85] lanes 48..63, s87 a literal on its way, s[88:89] kInv2Pi, s[90:93] compare
+        results."""
         t = FT
         NBAD, BANDS, ROT, N16, S, RR, Q = t, t + 1, (t + 2, t + 3, t + 4), t + 5, t + 6, t + 7, t + 8
         TS, AD, AD2 = t + 9, t + 10, t + 12
@@ -319,10 +321,11 @@ class PassFp16s:
                 op("v_fma_f64 %s, %s, %s, %s" % (v2(P + 2 * k), v2(TA), v2(D + 2 * k), v2(O + 2 * k)), uses=[ids["o", k], ids["d", k]])
             if c + 1 < NCT:
                 ids = part_a(c + 1)          # the loaded registers are free: the next tile's loads fly under this tile's encoding
-            # position not finite -> bit c of NBAD
-            op("v_cmp_class_f64 s[90:91], %s, s86" % v2(P))
-            op("v_cmp_class_f64 s[92:93], %s, s86" % v2(P + 2))
-            op("v_cmp_class_f64 vcc, %s, s86" % v2(P + 4))
+            # position outside the screen's box -> bit c of NBAD: not (|p| <= BOX) per coordinate, true of a NaN and of an
+            # infinity as well; BOX is a float64 inline constant
+            op("v_cmp_nle_f64 s[90:91], |%s|, %s" % (v2(P), BOX))
+            op("v_cmp_nle_f64 s[92:93], |%s|, %s" % (v2(P + 2), BOX))
+            op("v_cmp_nle_f64 vcc, |%s|, %s" % (v2(P + 4), BOX))
             op("s_or_b64 vcc, vcc, s[90:91]", "s_or_b64 vcc, vcc, s[92:93]", "v_cndmask_b32_e64 %s, 0, %d, vcc" % (V(NBAD if c == 0 else T1), 1 << c))
             if c:
                 op("v_or_b32 %s, %s, %s" % (V(NBAD), V(NBAD), V(T1)))
@@ -445,7 +448,7 @@ class PassFp16s:
                 else:
                     e.emit("v_accvgpr_write_b32 %s, %s" % (A(AKEEP + 8 * ct + i), V(H + 8 * ct + i)))
         if self.front:
-            for r, lit in ((84, 0), (85, 0xffff0000), (86, 0x207), (88, 0x6dc9c883), (89, 0x3fc45f30)):
+            for r, lit in ((84, 0), (85, 0xffff0000), (88, 0x6dc9c883), (89, 0x3fc45f30)):
                 e.emit("s_mov_b32 s%d, 0x%08x" % (r, lit))
         self.boundary(0)
         self.drain_dma(99)
@@ -544,7 +547,7 @@ def emit_pass(name, layers, out, cfg=None):
     if front:
         out.append("// The stream with the front end under it: P[0], P[1] of the four column tiles of THIS pass come in a%d..a%d and are copied to" % (ANEXT, N_AGPR - 1))
         out.append("// a%d..a%d; the same of the wave's next pass (samples snext + 16 ct + (lane & 15), clamped to mm1 = M - 1; nn = N, zz = its" % (AKEEP, AKEEP + 8 * NCT - 1))
-        out.append("// reciprocal word, udiv_word()) leave in them, with bit ct of nbad set where a position is not finite.  a%d..a%d are no operands:" % (ANEXT, N_AGPR - 1))
+        out.append("// reciprocal word, udiv_word()) leave in them, with bit ct of nbad set where a position is outside the box.  a%d..a%d are no operands:" % (ANEXT, N_AGPR - 1))
         out.append("// as operands hipcc carries them through the loop in VGPRs, 64 copies a pass.  They are clobbers of both statements, which")
         out.append("// makes them part of the kernel's allocation and keeps values of the compiler's out of them; the HIP code between two")
         out.append("// passes (sixteen lanes' stores) has no use for an AGPR.  %d front-end instructions in %d of the %d free MFMA gaps, %d" % (
@@ -568,6 +571,7 @@ def emit_pass(name, layers, out, cfg=None):
         out.append("// a%d..a%d by the stream; sigma[ct] (lanes 0..15) comes back in v%d..v%d.  The stream runs the whole ring protocol of one" % (AKEEP, AKEEP + 8 * NCT - 1, OUT, OUT + NCT - 1))
         out.append("// pass (entry, boundaries, walk to the padded end).")
         out.append("constexpr int kFp16sFrags = %d, kFp16sPadChunks = %d, kFp16sChunkBytes = %d, kFp16sTiles = %d;" % (gen.nfrag, gen.padc, CHUNK, NCT))
+        out.append("constexpr double kFp16sBox = %s;   // the box the in-stream front end tests positions against (kScreenBox)" % BOX)
         out.append("template <class Ring>")
         out.append("__device__ __forceinline__ void fp16s_asm_%s(const Ring& ring, lds_cptr bias_lane, half8 (&keep)[%d][2], float (&sigma)[%d]) {" % (name, NCT, NCT))
     out.append("    const unsigned src_lo = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring.src[0]), src_hi = __builtin_amdgcn_readfirstlane((unsigned)((size_t)ring.src[0] >> 32));")
