@@ -295,7 +295,8 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  *   of the count kernel at -m over the exact densities otherwise), or -1 while none has.
  * tgtc_net_screened_renders: how many chain renders screened their pass with this handle (-1 for NULL / no screen state).
  * tgtc_screen_list_fits / tgtc_screen_auto_decision: the two rules as pure host functions -- does a list of up to M indices
- *   and the 8192-byte scratch fit `bytes`; does AUTO screen pass 0 (coarse) / 1 (fine) on a landed (candidates, total).
+ *   and the 8192-byte scratch fit `bytes`; does AUTO screen pass 0 (coarse) / 1 (fine) / 2 (the sigma-only fine pass of the
+ *   chain geometry, below) on a landed (candidates, total).
  * The launches as entries of their own (tests, tools):
  *   tgtc_nerf_screen_rays: sigma [R,N] from the screen form (TGTC_ERR_UNSUPPORTED without a screen): NaN for exactly the
  *     samples outside the box or not finite, and for the others the bits of the sigma-only launch of a TGTC_PREC_FP16 handle
@@ -687,6 +688,43 @@ int tgtc_restyle_rays_folded_mx(const tgtc_net* fine, const tgtc_net* style, con
                                 const float* z, int K, int64_t R, int n_coarse, int n_fine, const void* cache, size_t cache_bytes,
                                 int64_t count, void* workspace, size_t workspace_bytes, float* rgb_fine, float* t_fine,
                                 void* stream);
+
+/* ------------------------------------------------------------------ the chain geometry: screened density passes for the
+ * culled stylised render and the geometry cache
+ * tgtc_render_rays_styled_sparse* and tgtc_geometry_build take their fine depths from the first half of the plain ray kernel
+ * and run a dense sigma-only fine pass.  The CHAIN GEOMETRY is a second ray-only half for the same calls: the passes of
+ * tgtc_render_rays_plain on TGTC_PATH_CHAIN without a coarse image -- tgtc_sample_coarse, the coarse sigma pass, the per-ray
+ * stage, a sigma-only fine pass -- each SCREENED where its handle's policy (tgtc_net_set_screen) says so:
+ *   coarse pass: as in the plain chain (an fp16x3 handle with a screen); list + scratch live in the first colour plane of the
+ *                workspace, which nothing uses before the zero-fill (dense where R x N x 12 bytes < R x n_coarse x 4 + 8192).
+ *   fine pass:   sigma only.  A fine handle in fp16x3 or fp16mx with a screen: the screen launch, the candidates' list, their
+ *                exact densities from tgtc_nerf_sigma_list (fp16x3) / tgtc_nerf_sigma_list_mx (fp16mx).  List + scratch are the
+ *                workspace's live[] and scratch, which the compaction at min_weight overwrites afterwards.  There is no colour
+ *                phase, so TGTC_CULL_* has no say.  AUTO is pass 2 of tgtc_screen_auto_decision, with a threshold of its own.
+ *   Screened or dense, each pass lands its candidate share in its handle's pinned word and counts in
+ *   tgtc_net_screened_renders; a handle without a screen (fp16, a coarse fp16mx) runs its pass dense.  No synchronisation.
+ * Identity: a screened call gives the BITS of the unscreened one (the argument of the density screen above), and t_fine is the
+ *   BITS of tgtc_render_rays_plain's on TGTC_PATH_CHAIN for the same handles, rays and jitter.  The fine depths agree with
+ *   those of the siblings without _chain only to rounding (two coarse kernels), so the chain geometry never replaces them
+ *   silently: it is a mode the caller asks for, and nothing selects it.
+ * tgtc_geometry_build_chain: the arguments, workspace, checks and errors of tgtc_geometry_build; the workspace feeds
+ *   tgtc_geometry_pack as before, and a cache does not know which geometry built it.
+ * tgtc_render_rays_styled_sparse_chain: `form`, then the arguments of tgtc_render_rays_styled_sparse.  form 0: z [K,R,32], the
+ *   workspace, handle rules and list launch of tgtc_render_rays_styled_sparse; 1: those of ..._folded (z [K,32]); 2: those of
+ *   ..._folded_mx.  Any other form -> TGTC_ERR_ARG.  The workspace size functions are the siblings', unchanged.
+ * tgtc_nerf_sigma_list_mx: tgtc_nerf_sigma_list for TGTC_PREC_FP16_FP6 handles (csrc/mlp_nerf_mx2.hip, the <IN_LIST, false>
+ *   instance): sigma[s] of the listed samples, the bits of tgtc_nerf_forward_rays(rgb = NULL) and of the full kernels' sigma,
+ *   nothing else touched.  Any other precision -> TGTC_ERR_UNSUPPORTED (tgtc_nerf_sigma_list keeps refusing fp16mx). */
+int tgtc_nerf_sigma_list_mx(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                            const uint32_t* live, const uint32_t* n_live, float* sigma, void* stream);
+int tgtc_geometry_build_chain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R,
+                              int n_coarse, int n_fine, float near_, float far_, const float* jitter, float min_weight,
+                              void* workspace, size_t workspace_bytes, float* t_fine, uint32_t* live_count, void* stream);
+int tgtc_render_rays_styled_sparse_chain(int form, const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                         const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                         int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                         float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                         float* t_fine, uint32_t* live_count, void* stream);
 
 #ifdef __cplusplus
 }

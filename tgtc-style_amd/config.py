@@ -47,6 +47,7 @@ EXTRA = {
     "geometry_cache": (str, ""),       # --share_geometry: directory of cached ray geometry, reused across runs (HELP below)
     "fold_latents": (None, False),     # --share_geometry with --cull_weight or --geometry_cache: one latent per (style, frame) (HELP below)
     "style_precision": (str, ""),      # --fold_latents with a fine network in fp16mx: "fp16mx" runs the style networks in fp16mx (HELP below)
+    "chain_geometry": (None, False),   # --share_geometry with --cull_weight or --geometry_cache: the plain chain's screened passes (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
     "origin_train": (None, False),     # run the reference's Origin_train loop on the HIP training kernels (HELP below)
@@ -118,6 +119,14 @@ HELP = {
                        "--geometry_cache the frames are restyled from the cached geometry in the same kernel: no trunk "
                        "plane is built or saved, and the files and keys of the directory are those of the run without the "
                        "flag.  Default empty: off",
+    "chain_geometry": "with --render_valid_style --share_geometry and either --cull_weight >= 0 or --geometry_cache (refused "
+                      "otherwise): take the ray-only half of every call -- fine depths, densities, weights -- from the "
+                      "passes of the plain chain render instead of the ray kernel's first half and a dense density pass.  "
+                      "Each of the two density passes then runs the density screen where its network has one and the "
+                      "library's rule says it pays: fp16 densities of every sample, the exact kernel on the candidates only; "
+                      "screened or not, the images are the same bits.  Against a run without the flag the fine depths "
+                      "differ by the rounding between two coarse kernels, so the cache keys carry geometry=chain and a "
+                      "--geometry_cache directory never serves one run's files to the other.  Default: off",
 }
 
 

@@ -321,6 +321,18 @@ int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double
     return nerf_x3s_list_launch(a, st);
 }
 
+// The same for fp16mx handles: the bits of their sigma-only launch over rays and of the FULL kernels' sigma
+// (mlp_nerf_mx2.hip, the <IN_LIST, false> instance; the caller has checked the precision and R x N < 2^31)
+int nerf_sigma_list_mx_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                            const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.sigma = sigma;
+    a.live = live, a.n_live = n_live;
+    a.bias = net->dev;
+    a.stream = net->dev + net->bias_bytes;
+    return nerf_mx2_launch(IN_LIST, false, a, st);
+}
+
 // The density screen: sigma of every sample from the handle's TGTC_PREC_FP16 form, one MFMA product per
 // weight (the caller has checked that the screen is enabled).  Its kernel is the four-tile persistent stream of
 // mlp_nerf_fp16s.hip; with TGTC_SCREEN_CFGFAST=1 in the environment (read at every call: the yardstick the stream is held
@@ -601,6 +613,18 @@ extern "C" int tgtc_nerf_sigma_list(const tgtc_net* net, const double* rays_o, c
     if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
         return fail(TGTC_ERR_UNSUPPORTED, "nerf_sigma_list: R x N >= 2^31 (chunk the rays)");
     return nerf_sigma_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, sigma, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_sigma_list_mx(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                                       int N, const uint32_t* live, const uint32_t* n_live, float* sigma, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_sigma_list_mx: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && live && n_live && sigma, "nerf_sigma_list_mx: null pointer");
+    if (net->precision != TGTC_PREC_FP16_FP6)
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_sigma_list_mx: built for fp16+fp6 handles only (got precision %d)", net->precision);
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_sigma_list_mx: R x N >= 2^31 (chunk the rays)");
+    return nerf_sigma_list_mx_impl(net, rays_o, rays_d, ts, R, N, live, n_live, sigma, as_stream(stream));
 }
 
 extern "C" int tgtc_net_destroy(tgtc_net* net) {

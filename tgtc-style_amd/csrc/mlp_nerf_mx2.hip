@@ -27,6 +27,8 @@ using CfgMx2 = MlpCfg<4, 2, false, 4>;
 // of passes follows from *n_live read HERE (the host's n_pass is ignored, the grid is the CU count), a workgroup without
 // a pass still runs the ring prologue and the final wait; rgb is stored, scattered to rgb[live[slot]], and -- where a.sigma
 // is set -- sigma to sigma[live[slot]].
+// <IN_LIST, false> (the exact phase of the screened sigma-only fine pass of the chain geometry, render.hip): the same walk of
+// the list around the sigma stream; sigma[live[slot]] alone is stored, the bits of <IN_RAYS, false> and of the FULL kernels.
 template <int IN_MODE, bool FULL>
 __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long n_pass) {
     using C = CfgMx2;
@@ -114,8 +116,10 @@ __global__ void __launch_bounds__(256, 1) nerf_mx2_kernel(NerfArgs a, long long 
                         const unsigned s = a.live[slot];
                         if (s < a.M) {   // (a list that keeps its promise never fails this)
                             if (a.sigma) a.sigma[s] = sigma[c];   // (the screened fine pass: the candidates' exact densities)
+                            if constexpr (FULL) {
 #pragma unroll
-                            for (int r = 0; r < 3; ++r) a.rgb[(size_t)s * 3 + r] = 1.0f / (1.0f + expf(-rgb[c][r]));   // models.py:111
+                                for (int r = 0; r < 3; ++r) a.rgb[(size_t)s * 3 + r] = 1.0f / (1.0f + expf(-rgb[c][r]));   // models.py:111
+                            }
                         }
                     }
                     continue;
@@ -149,6 +153,7 @@ int nerf_mx2_launch(int in_mode, bool full, const NerfArgs& a, hipStream_t st) {
         case IN_PTS * 2 + 1: nerf_mx2_kernel<IN_PTS, true><<<nwg, block, 0, st>>>(a, n_pass); break;
         case IN_ENC * 2 + 1: nerf_mx2_kernel<IN_ENC, true><<<nwg, block, 0, st>>>(a, n_pass); break;
         // the list's length is on the device: one workgroup per CU (never more than the dense plane has passes), each reads it
+        case IN_LIST * 2 + 0: nerf_mx2_kernel<IN_LIST, false><<<nwg, block, 0, st>>>(a, 0); break;
         case IN_LIST * 2 + 1: nerf_mx2_kernel<IN_LIST, true><<<nwg, block, 0, st>>>(a, 0); break;
         default: return fail(TGTC_ERR_UNSUPPORTED, "nerf (fp16+fp6, two tiles): no kernel for input mode %d, full %d", in_mode, (int)full);
     }

@@ -41,6 +41,8 @@ int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const doub
                            const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st);
 int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                          const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st);
+int nerf_sigma_list_mx_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                            const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st);
 int nerf_screen_rays_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                           float* sigma, hipStream_t st);
 int launch_compact_candidates(const float* sigma, int64_t M, float margin, uint32_t* live, uint32_t* scratch, hipStream_t st);
@@ -165,6 +167,7 @@ enum : unsigned {
     kFold = 1,    // frame-constant latents z [K,32], folded into K bias tables at the end of the workspace
     kMx = 2,      // the fp16mx form of the entry (its own rule for the handles' precisions, its own launch)
     kPlane = 4,   // a restyle from the trunk plane: no NeRF handle
+    kChain = 8,   // the chain geometry: the ray-only half from the plain chain's passes, screened where the handles say so
 };
 
 // the reference dereferences None when N_samples_fine == 0; require it instead
@@ -349,6 +352,20 @@ static bool cull_wanted(const tgtc_cull_state* c) {
 // frames once a share has landed.
 constexpr float kScreenCoarseThreshold = 0.56f;
 constexpr float kScreenFineThreshold = 0.45f;
+// Pass 2, the sigma-only fine pass of the chain geometry (fine_sigma_pass below): there is no colour phase, so the
+// break-even is another one -- the screen launch plus C x the SIGMA list launch against the dense sigma-only launch s,
+// C* = (s - p) / l -- derived by the same recipe.  Measured on the MI355X (tools/time_screen_geometry.py --step0,
+// profiles/screen_geometry_timing.json "step0") on the fine depths of a real 400 x 400 render (pose 5) at 128 + 64, for both
+// precisions a fine handle is screened in:
+//   fp16mx: p = 18.89 ms, s = 42.85 ms, the sigma list launch (nerf_mx2_kernel<IN_LIST, false>) 1.423 ns per listed sample
+//           (l = 43.73 ms): C* = 0.548.  Candidate share over the orbit (spiral_pose 0 .. 119) 0.112 .. 0.142, spread 0.030;
+//           the extra launches (two compaction kernels, the statistic's kernel and copy: the 0.3 ms of the fine pass above is
+//           an upper bound, and the dense form takes its statistic too) 0.007 of l.  0.548 - 0.030 - 0.007 = 0.51.
+//   fp16x3: p = 18.76 ms, s = 58.33 ms, the sigma list launch (nerf_x3s_kernel<IN_LIST>) 1.976 ns per listed sample
+//           (l = 60.71 ms): C* = 0.652.  Orbit 0.113 .. 0.143, spread 0.030; launches 0.005.  0.652 - 0.030 - 0.005 = 0.61.
+// The precisions differ; pass 2 keeps the smaller threshold for both.  It clears the orbit's share (0.143) by a wide margin:
+// AUTO screens the sigma-only fine pass of the benchmark's frames once a share has landed.
+constexpr float kScreenFineSigmaThreshold = 0.51f;
 
 static bool screen_enabled(const tgtc_net* net) { return net->screen && net->screen->dev && net->screen->landed; }
 
@@ -357,9 +374,10 @@ extern "C" int tgtc_screen_list_fits(size_t bytes, int64_t M) {
     return M >= 0 && M < ((int64_t)1 << 31) && bytes >= (size_t)M * 4 + kSparseScratchBytes;
 }
 
-// AUTO's rule, pure host code: screen iff a share has landed and lies below the threshold of the pass (0: coarse, 1: fine)
+// AUTO's rule, pure host code: screen iff a share has landed and lies below the threshold of the pass (0: coarse, 1: fine,
+// 2: the sigma-only fine pass of the chain geometry)
 extern "C" int tgtc_screen_auto_decision(int pass, uint32_t candidates, uint32_t total) {
-    const float thr = pass == 0 ? kScreenCoarseThreshold : kScreenFineThreshold;
+    const float thr = pass == 0 ? kScreenCoarseThreshold : pass == 2 ? kScreenFineSigmaThreshold : kScreenFineThreshold;
     return total != 0 && candidates <= total && (double)candidates < (double)thr * (double)total;
 }
 
@@ -380,9 +398,10 @@ static int land_share(uint32_t* scratch, int64_t M, volatile uint64_t* landed, h
 
 // The coarse pass of a plain chain render that wants no coarse image: sigma_c alone.  Screened where the coarse handle (fp16x3)
 // has a screen and its policy says so: the list and the 8 KiB of scratch live in the fine colour plane, which nothing uses
-// before the fine pass; where they do not fit, the pass is dense.
+// before the fine pass; where they do not fit, the pass is dense.  WS: any workspace with ts_c, sigma_c and rgb_f.
+template <class WS>
 static int coarse_sigma_pass(const tgtc_net* coarse, const double* rays_o, const double* rays_d, int64_t R, int nc,
-                             const RenderWorkspace& ws, size_t rgb_f_bytes, hipStream_t st) {
+                             const WS& ws, size_t rgb_f_bytes, hipStream_t st) {
     const int64_t M = R * (int64_t)nc;
     tgtc_screen_state* const sc = coarse->precision == TGTC_PREC_FP16X3 && screen_enabled(coarse) ? coarse->screen : nullptr;
     char* const spare = reinterpret_cast<char*>(ws.rgb_f);
@@ -641,22 +660,73 @@ extern "C" size_t tgtc_render_styled_sparse_workspace_bytes(int64_t R, int n_coa
     return SparseWorkspace(nullptr, R, n_coarse, n_fine, K).total;
 }
 
+// The sigma-only fine pass of the chain geometry: sigma_f of every fine sample, nothing else.  Screened where the fine handle
+// (fp16x3 or fp16mx) has a screen and its policy says so (pass 2 of tgtc_screen_auto_decision; no colour phase exists here,
+// so the cull mode has no say): fp16 densities of all samples, the candidates' list, their exact densities from the sigma
+// list launch of the handle's precision.  The list and the scratch are sw.live / sw.scratch, which the compaction at
+// min_weight overwrites afterwards: they always fit.  Screened or dense, the candidate share lands in the handle's pinned word.
+static int fine_sigma_pass(const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R, int nt,
+                           const SparseWorkspace& sw, hipStream_t st) {
+    const int64_t M = R * (int64_t)nt;
+    const bool listable = (fine->precision == TGTC_PREC_FP16X3 || fine->precision == TGTC_PREC_FP16_FP6) && M < kIndexLimit;
+    tgtc_screen_state* const sc = listable && screen_enabled(fine) ? fine->screen : nullptr;
+    int rc;
+    if (sc && screen_wanted(sc, 2)) {
+        rc = nerf_screen_rays_impl(fine, rays_o, rays_d, sw.m.ts_f, R, nt, sw.m.sigma_f, st);
+        if (rc) return rc;
+        rc = launch_compact_candidates(sw.m.sigma_f, M, sc->margin, sw.live, sw.scratch, st);
+        if (rc) return rc;
+        rc = (fine->precision == TGTC_PREC_FP16_FP6 ? nerf_sigma_list_mx_impl : nerf_sigma_list_impl)(
+            fine, rays_o, rays_d, sw.m.ts_f, R, nt, sw.live, sw.scratch, sw.m.sigma_f, st);
+        if (rc) return rc;
+        ++sc->screened;
+        return land_share(sw.scratch, M, sc->landed, st);
+    }
+    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, sw.m.ts_f, R, nt, nullptr, sw.m.sigma_f, st);
+    if (rc) return rc;
+    if (sc) {
+        ++sc->dense;
+        if (sc->mode != TGTC_SCREEN_OFF) {
+            rc = launch_count_candidates(sw.m.sigma_f, M, sc->margin, sw.scratch, st);
+            if (rc) return rc;
+            return land_share(sw.scratch, M, sc->landed, st);
+        }
+    }
+    return TGTC_OK;
+}
+
 // Steps 1-4 of the culled stylised render, the half that depends on the ray alone (tgtc_render_rays_styled_sparse and
 // tgtc_geometry_build): fine depths ts_f, sigma_f, the depth image, the weights plane w_f, the ascending list live[] of the
 // samples with w_f > min_weight and its length (scratch word 0, and *live_count where given).
-static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d, int64_t R,
-                        int n_coarse, int n_fine, float near_, float far_, const float* jitter, float min_weight,
+// chain: steps 1 and 2 are the PLAIN CHAIN's passes (tgtc_render_rays_plain without a coarse image) -- coarse depths, the coarse
+// sigma pass, the per-ray stage, the sigma-only fine pass -- each screened where its handle's policy says so; the coarse list
+// lives in the first colour plane, which nothing uses before step 5.  The depths are those of the plain chain bit for bit,
+// and agree with the ray kernel's first half (chain = false) only to rounding: the caller asks for one or the other.
+static int ray_geometry(bool chain, const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
+                        int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter, float min_weight,
                         const SparseWorkspace& sw, float* t_fine, uint32_t* live_count, void* stream) {
     const MultiWorkspace& ws = sw.m;
     const int nt = n_coarse + n_fine;
     hipStream_t st = as_stream(stream);
-    // 1. geometry half, as tgtc_render_rays_styled_multi
-    int rc = fine_depths(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws, stream);
-    if (rc) return rc;
-    // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
-    //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
-    rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
-    if (rc) return rc;
+    int rc;
+    if (chain) {
+        rc = tgtc_sample_coarse(rays_o, rays_d, R, n_coarse, near_, far_, jitter, nullptr, ws.ts_c, stream);
+        if (rc) return rc;
+        rc = coarse_sigma_pass(coarse, rays_o, rays_d, R, n_coarse, ws, (size_t)R * nt * 3 * sizeof(float), st);
+        if (rc) return rc;
+        rc = coarse_to_fine(nullptr, ws.sigma_c, ws.ts_c, ws.w_c, rays_o, rays_d, R, n_coarse, n_fine, nullptr, nullptr, ws.ts_f, st);
+        if (rc) return rc;
+        rc = fine_sigma_pass(fine, rays_o, rays_d, R, nt, sw, st);
+        if (rc) return rc;
+    } else {
+        // 1. geometry half, as tgtc_render_rays_styled_multi
+        rc = fine_depths(coarse, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, ws, stream);
+        if (rc) return rc;
+        // 2. sigma of every fine sample (the sigma-only NeRF launch carries the bits of the styled kernels' sigma:
+        //    tests/test_sparse_style_gpu.py, test_sigma_pass_bits_of_the_styled_kernel)
+        rc = nerf_forward_rays_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, nullptr, ws.sigma_f, st);
+        if (rc) return rc;
+    }
     // 3. depth image and the weights plane
     rc = launch_composite(nullptr, ws.sigma_f, ws.ts_f, R, nt, nullptr, t_fine, sw.w_f, st);
     if (rc) return rc;
@@ -672,6 +742,7 @@ static int ray_geometry(const tgtc_net* coarse, const tgtc_net* fine, const doub
 // The body of the three tgtc_render_rays_styled_sparse* entries.  flags: 0 is the per-ray form, z [K,R,32]; kFold the
 // frame-constant one, z [K,32] folded into K bias tables in one more plane at the end of the workspace; kFold | kMx that
 // for the fp16x3+fp16mx pair.  They differ in the rule for the handles' precisions and in the list launch, nothing else.
+// kChain on top of any of the three: the chain geometry (ray_geometry), tgtc_render_rays_styled_sparse_chain.
 static int render_rays_culled(const char* who, unsigned flags, const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
                               const double* rays_o, const double* rays_d, const float* z, int K, int64_t R, int n_coarse,
                               int n_fine, float near_, float far_, const float* jitter, float min_weight, void* workspace,
@@ -707,8 +778,8 @@ static int render_rays_culled(const char* who, unsigned flags, const tgtc_net* c
         if (rc) return rc;
     }
     // 1-4. everything that depends on the ray alone
-    rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine, live_count,
-                      stream);
+    rc = ray_geometry(flags & kChain, coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, t_fine,
+                      live_count, stream);
     if (rc) return rc;
     // 5. dead samples keep colour +0
     TGTC_HIP_CHECK(hipMemsetAsync(ws.rgb_f, 0, (size_t)K * R * nt * 3 * sizeof(float), st));
@@ -742,27 +813,36 @@ extern "C" int tgtc_render_rays_styled_sparse(const tgtc_net* coarse, const tgtc
 
 // Steps 1-4 of tgtc_render_rays_styled_sparse on the sparse workspace at K = 1.  The depth image also stays in the
 // workspace (the first R floats of the colour plane, which no step of the build uses), where tgtc_geometry_pack reads it.
-extern "C" int tgtc_geometry_build(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
-                                   int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
-                                   float min_weight, void* workspace, size_t workspace_bytes, float* t_fine,
-                                   uint32_t* live_count, void* stream) {
-    TGTC_REQUIRE(min_weight >= 0.0f, "geometry_build: min_weight must be >= 0 and not NaN (got %g)", (double)min_weight);
-    TGTC_REQUIRE(coarse && fine && R >= 0, "geometry_build: bad argument");
-    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0, "geometry_build: coarse and fine must be NeRF handles");
+// The body of tgtc_geometry_build and (chain) tgtc_geometry_build_chain.
+static int geometry_build(const char* who, bool chain, const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o,
+                          const double* rays_d, int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                          float min_weight, void* workspace, size_t workspace_bytes, float* t_fine, uint32_t* live_count,
+                          void* stream) {
+    TGTC_REQUIRE(min_weight >= 0.0f, "%s: min_weight must be >= 0 and not NaN (got %g)", who, (double)min_weight);
+    TGTC_REQUIRE(coarse && fine && R >= 0, "%s: bad argument", who);
+    TGTC_REQUIRE(coarse->kind == 0 && fine->kind == 0, "%s: coarse and fine must be NeRF handles", who);
     TGTC_REQUIRE(n_coarse >= 3 && n_fine >= 1, "render: need n_coarse >= 3 and n_fine >= 1 (got %d, %d)", n_coarse, n_fine);
     if (R == 0) return TGTC_OK;
-    TGTC_REQUIRE(rays_o && rays_d && workspace && live_count, "geometry_build: null pointer");
+    TGTC_REQUIRE(rays_o && rays_d && workspace && live_count, "%s: null pointer", who);
     const int nt = n_coarse + n_fine;
     if (R * nt >= ((int64_t)1 << 31))
-        return fail(TGTC_ERR_UNSUPPORTED, "geometry_build: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)");
+        return fail(TGTC_ERR_UNSUPPORTED, "%s: R x (n_coarse + n_fine) >= 2^31 (chunk the rays)", who);
     SparseWorkspace sw(static_cast<char*>(workspace), R, n_coarse, n_fine, 1);
-    TGTC_REQUIRE(workspace_bytes >= sw.total, "geometry_build: workspace of %zu bytes, need %zu", workspace_bytes, sw.total);
-    int rc = ray_geometry(coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, sw.m.rgb_f,
+    TGTC_REQUIRE(workspace_bytes >= sw.total, "%s: workspace of %zu bytes, need %zu", who, workspace_bytes, sw.total);
+    int rc = ray_geometry(chain, coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight, sw, sw.m.rgb_f,
                           live_count, stream);
     if (rc) return rc;
     if (t_fine)
         TGTC_HIP_CHECK(hipMemcpyAsync(t_fine, sw.m.rgb_f, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
     return TGTC_OK;
+}
+
+extern "C" int tgtc_geometry_build(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
+                                   int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                   float min_weight, void* workspace, size_t workspace_bytes, float* t_fine,
+                                   uint32_t* live_count, void* stream) {
+    return geometry_build("geometry_build", false, coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter, min_weight,
+                          workspace, workspace_bytes, t_fine, live_count, stream);
 }
 
 extern "C" size_t tgtc_geometry_cache_bytes(int64_t R, int64_t count) {
@@ -1060,3 +1140,28 @@ extern "C" int tgtc_restyle_rays_folded_mx(const tgtc_net* fine, const tgtc_net*
                         cache_bytes, count, nullptr, 0, workspace, workspace_bytes, rgb_fine, t_fine, stream);
 }
 
+// ------------------------------------------------------------------------------------------------ the chain geometry
+// The culled stylised render and the geometry build with their ray-only half taken from the plain chain's passes
+// (ray_geometry, chain), each screened where its handle's policy says so (tgtc_net_set_screen).  A mode the
+// caller asks for: the depths are the plain chain's, which the ray kernel's first half matches only to rounding.  The
+// same bodies as the siblings, with kChain; every check, workspace and order of work is theirs.
+extern "C" int tgtc_geometry_build_chain(const tgtc_net* coarse, const tgtc_net* fine, const double* rays_o, const double* rays_d,
+                                         int64_t R, int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                         float min_weight, void* workspace, size_t workspace_bytes, float* t_fine,
+                                         uint32_t* live_count, void* stream) {
+    return geometry_build("geometry_build_chain", true, coarse, fine, rays_o, rays_d, R, n_coarse, n_fine, near_, far_, jitter,
+                          min_weight, workspace, workspace_bytes, t_fine, live_count, stream);
+}
+
+// form: 0 the per-ray form (z [K,R,32]), 1 the folded one (z [K,32]), 2 the folded one for the fp16x3+fp16mx pair
+extern "C" int tgtc_render_rays_styled_sparse_chain(int form, const tgtc_net* coarse, const tgtc_net* fine, const tgtc_net* style,
+                                                    const double* rays_o, const double* rays_d, const float* z, int K, int64_t R,
+                                                    int n_coarse, int n_fine, float near_, float far_, const float* jitter,
+                                                    float min_weight, void* workspace, size_t workspace_bytes, float* rgb_fine,
+                                                    float* t_fine, uint32_t* live_count, void* stream) {
+    TGTC_REQUIRE(form >= 0 && form <= 2, "render_rays_styled_sparse_chain: form is 0 (per ray), 1 (folded) or 2 (folded, fp16mx); got %d",
+                 form);
+    const unsigned flags = kChain | (form == 0 ? 0u : form == 1 ? (unsigned)kFold : (unsigned)(kFold | kMx));
+    return render_rays_culled("render_rays_styled_sparse_chain", flags, coarse, fine, style, rays_o, rays_d, z, K, R, n_coarse, n_fine,
+                              near_, far_, jitter, min_weight, workspace, workspace_bytes, rgb_fine, t_fine, live_count, stream);
+}

@@ -80,6 +80,13 @@ _SIGNATURES = {
     "tgtc_nerf_sigma_list": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_forward_list_sigma": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p],
+    # the chain geometry (include/tgtc_hip.h, last section): the siblings' argument lists, `form` in front of the render's
+    "tgtc_nerf_sigma_list_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_geometry_build_chain": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_float,
+                                  c_void_p, c_size_t, c_void_p, c_void_p, c_void_p],
+    "tgtc_render_rays_styled_sparse_chain": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                             c_int, c_float, c_float, c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p,
+                                             c_void_p, c_void_p],
     "tgtc_composite": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_train": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_composite_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,

@@ -161,7 +161,9 @@ class RayRenderer:
         (TGTC_SCREEN_AUTO), True forces it wherever it fits, False switches it off; one value for both passes, or a pair
         (coarse, fine).  cull=False switches the fine screen off as well.  The same bits again: measured for samples inside the
         screen's box |x|, |y|, |z| <= 2, where its margin is calibrated; a sample outside it is always handed to the exact
-        kernel, so near / far beyond NDC cost time, not bits (DESIGN 3.1 "The screen's domain")."""
+        kernel, so near / far beyond NDC cost time, not bits (DESIGN 3.1 "The screen's domain").
+        The culled stylised calls and build_geometry use `screen` only under geometry="chain" (DESIGN 3.1i): there the fine
+        screen covers a fine handle in fp16x3 as well and does not depend on `cull`."""
         if isinstance(screen, tuple):
             if len(screen) != 2 or any(v not in self._SCREEN for v in screen):
                 raise ValueError("screen must be None, True, False or a pair of those (coarse, fine)")
@@ -185,12 +187,15 @@ class RayRenderer:
         """Put this renderer's `cull` on the fine handle (a host call; handles are repacked when weights change)."""
         self.fine.packed().set_cull(self._CULL[self.cull])
 
-    def apply_screen(self):
+    def apply_screen(self, chain=False):
         """Put this renderer's `screen` on the two handles, enabling the screen where a pass may be screened (host calls;
-        handles are repacked when weights change).  Handles in fp16 have no screen."""
+        handles are repacked when weights change).  Handles in fp16 have no screen.
+        chain: the call is a chain geometry (geometry="chain"), whose sigma-only fine pass is screened for a fine handle in
+        fp16x3 as well; plain renders screen a fine handle in fp16mx only."""
         pair = self.screen if isinstance(self.screen, tuple) else (self.screen, self.screen)
-        for net, want, prec in ((self.coarse.packed(), pair[0], "fp16x3"), (self.fine.packed(), pair[1], "fp16mx")):
-            if net.precision != prec:
+        fine_precs = ("fp16mx", "fp16x3") if chain else ("fp16mx",)
+        for net, want, precs in ((self.coarse.packed(), pair[0], ("fp16x3",)), (self.fine.packed(), pair[1], fine_precs)):
+            if net.precision not in precs:
                 continue
             if want is not False and not net.screen_tried:
                 net.enable_screen()
@@ -274,6 +279,16 @@ class RayRenderer:
         return ws
 
     @staticmethod
+    def _check_geometry(who, geometry, min_weight):
+        """geometry: None (the ray kernel's first half and a dense sigma pass, today's call) or "chain" (the plain chain's
+        passes, screened as `screen` says; the culled calls only).  ValueError otherwise; True for "chain"."""
+        if geometry not in (None, "chain"):
+            raise ValueError("%s: geometry is None or 'chain', got %r" % (who, geometry))
+        if geometry is not None and min_weight is None:
+            raise ValueError("%s: geometry='chain' needs a min_weight (the culled render)" % who)
+        return geometry == "chain"
+
+    @staticmethod
     def _check_zs(zs, R):
         """zs [K,R,32] (per ray) or [K,32] (frame-constant: folded) as contiguous float32, then K and whether it is folded."""
         zs = zs.to(torch.float32).contiguous()
@@ -286,18 +301,20 @@ class RayRenderer:
         return zs, zs.shape[0], folded
 
     def render(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, z=None, want_coarse=False,
-               min_weight=None):
+               min_weight=None, geometry=None):
         """rays_o, rays_d float64 [R,3] on the GPU -> dict rgb [R,3], t [R] (+ rgb_coarse, t_coarse).
 
         min_weight (stylised render only, a float >= 0): the style networks run only on the fine samples whose compositing
-        weight exceeds it -- `render_latents(..., min_weight=...)` with K = 1, returning rgb [R,3], t [R] and "live"."""
+        weight exceeds it -- `render_latents(..., min_weight=...)` with K = 1, returning rgb [R,3], t [R] and "live".
+        geometry (with a min_weight only): handed to render_latents."""
+        self._check_geometry("render", geometry, min_weight)
         if min_weight is not None:
             if want_coarse:
                 raise ValueError("min_weight and want_coarse exclude each other (the culled render has no coarse image)")
             if self.style is None or z is None:
                 raise ValueError("min_weight belongs to the stylised render: it needs a style pair and z")
             out = self.render_latents(rays_o, rays_d, n_coarse, n_fine, near=near, far=far, jitter=jitter,
-                                      zs=z.unsqueeze(0), min_weight=min_weight)
+                                      zs=z.unsqueeze(0), min_weight=min_weight, geometry=geometry)
             out["rgb"] = out["rgb"][0]
             return out
         hip.require_gpu(rays_o, rays_d)
@@ -353,7 +370,7 @@ class RayRenderer:
         return ts
 
     def render_latents(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, zs=None, min_weight=None,
-                       style_precision=None):
+                       style_precision=None, geometry=None):
         """The same rays under K latent sets in one call: zs float [K,R,32] -> dict rgb [K,R,3], t [R].
 
         The coarse pass, the fine depths and the fine NeRF trunk run once and are shared by the K images (one launch of
@@ -378,7 +395,15 @@ class RayRenderer:
         and the K latents (the pair's fp16mx streams, packed at the first such call) of every tile of the list in one kernel.
         It needs zs [K,32], a min_weight, a fine handle in fp16mx and an fp16x3 style pair: anything else is a ValueError
         before any launch.  rgb, t are the bits of build_geometry(min_weight, keep_trunk=True, trunk_precision="fp16x3") +
-        restyle(style_precision="fp16mx"), without the plane.  No default selects it."""
+        restyle(style_precision="fp16mx"), without the plane.  No default selects it.
+
+        geometry: None is the calls above.  "chain" (with a min_weight; anything else is a ValueError before any launch) takes
+        the ray-only half from the plain chain's passes instead of the ray kernel's first half and a dense sigma pass
+        (tgtc_render_rays_styled_sparse_chain, in the form the other arguments select): coarse pass and sigma-only fine pass are
+        screened as this renderer's `screen` says (apply_screen is called first; a fine handle in fp16x3 gets its screen too).
+        Screened or not the results are the same bits, and t is the bits of `RayRenderer(..., fused=False).render(...)` without
+        a style; against geometry=None the depths differ by the rounding between two coarse kernels.  No default selects it."""
+        chain = self._check_geometry("render_latents", geometry, min_weight)
         if style_precision not in (None, "fp16mx"):
             raise ValueError("render_latents: style_precision is None or 'fp16mx', got %r" % (style_precision,))
         mx = style_precision == "fp16mx"
@@ -419,6 +444,10 @@ class RayRenderer:
             if mx:
                 self.style.packed().enable_mx()                     # a no-op from the second call on
                 call = lib.tgtc_render_rays_styled_sparse_folded_mx
+            if chain:
+                self.apply_screen(chain=True)
+                form = 2 if mx else 1 if folded else 0
+                call = lambda *a: lib.tgtc_render_rays_styled_sparse_chain(form, *a)
             hip.check(call(self.coarse.packed().handle, self.fine.packed().handle, self.style.packed().handle, hip.ptr(rays_o),
                            hip.ptr(rays_d), hip.ptr(zs), K, R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter),
                            min_weight, hip.ptr(ws), ws.numel(), hip.ptr(rgb), hip.ptr(t), hip.ptr(live), hip.stream()))
@@ -430,12 +459,16 @@ class RayRenderer:
         return {"rgb": rgb, "t": t}
 
     def build_geometry(self, rays_o, rays_d, n_coarse, n_fine, near=0., far=1., jitter=None, min_weight=0., key=None,
-                       keep_trunk=False, trunk_precision=None):
+                       keep_trunk=False, trunk_precision=None, geometry=None):
         """Everything of `render_latents(..., min_weight=min_weight)` that depends on the rays alone -- coarse pass, fine
         depths, sigma pass, weights, compaction -- as a GeometryCache (about 12 bytes per live sample + 8 per ray).  The
         host reads the live count once here (one synchronisation per build); `restyle` has none.
         keep_trunk: also `build_trunk` the cache (1 KiB per live sample in fp16x3, 512 B in fp16); trunk_precision goes to
-        `build_trunk`."""
+        `build_trunk`.
+        geometry: None, or "chain" for the chain geometry of render_latents (tgtc_geometry_build_chain; anything else is a
+        ValueError before any launch).  The cache is the one `render_latents(..., geometry="chain")` would use; `restyle`
+        does not know which geometry built a cache."""
+        chain = self._check_geometry("build_geometry", geometry, min_weight)
         hip.require_gpu(rays_o, rays_d)
         lib = hip.load()
         if n_fine <= 0:
@@ -447,9 +480,12 @@ class RayRenderer:
         ws = self._scratch("_ws_multi", lib.tgtc_render_styled_sparse_workspace_bytes(R, n_coarse, n_fine, 1), dev)
         jitter = self._jitter(jitter)
         live = torch.zeros((), device=dev, dtype=torch.int32)
-        hip.check(lib.tgtc_geometry_build(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
-                                          R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), min_weight, hip.ptr(ws),
-                                          ws.numel(), None, hip.ptr(live), hip.stream()))
+        if chain:
+            self.apply_screen(chain=True)
+        build = lib.tgtc_geometry_build_chain if chain else lib.tgtc_geometry_build
+        hip.check(build(self.coarse.packed().handle, self.fine.packed().handle, hip.ptr(rays_o), hip.ptr(rays_d),
+                        R, n_coarse, n_fine, float(near), float(far), hip.ptr(jitter), min_weight, hip.ptr(ws),
+                        ws.numel(), None, hip.ptr(live), hip.stream()))
         count = int(live)
         buf = torch.zeros(lib.tgtc_geometry_cache_bytes(R, count), dtype=torch.uint8, device=dev)   # padding bytes: 0 in the file
         hip.check(lib.tgtc_geometry_pack(hip.ptr(ws), R, n_coarse, n_fine, min_weight, count, hip.ptr(buf), buf.numel(),
@@ -774,7 +810,7 @@ def _cached_geometry(renderer, directory, name, key, build):
 
 
 def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=None, geometry_cache=None,
-                         geometry_tag=None, fold_latents=False, style_precision=None):
+                         geometry_tag=None, fold_latents=False, style_precision=None, geometry=None):
     """render_style with share_geometry: walk the FRAMES of the validation path and render all styles of a frame in one
     `RayRenderer.render_latents` call (shared coarse pass, fine depths and fine NeRF trunk), under the jitter of the frame's
     style-0 image.  Same file names as the per-image walk.  The dataset supplies the frames through its `frame_batches`
@@ -788,8 +824,16 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     restyle: the folded kernels); needs a min_weight or a geometry_cache, and every ray of a call in the same frame.
     style_precision: None, or "fp16mx" for a renderer whose fine handle is in fp16mx (fold_latents only): handed to
     RayRenderer.render_latents, or with a geometry_cache to RayRenderer.restyle on a cache without a plane.  The geometry key
-    does not change: it describes the NeRF half only."""
+    does not change: it describes the NeRF half only.
+    geometry: None, or "chain" (needs a min_weight or a geometry_cache): RayRenderer.render_latents' / build_geometry's.  The
+    tag of the cache keys gains "geometry=chain", so a directory never serves a cache of one geometry to a run of the other."""
     ds = dataloader.dataset
+    if geometry not in (None, "chain"):
+        raise ValueError("geometry is None or 'chain', got %r" % (geometry,))
+    if geometry is not None and min_weight is None and geometry_cache is None:
+        raise ValueError("geometry='chain' needs a min_weight or a geometry_cache (it is the geometry of the culled render)")
+    if geometry is not None:
+        geometry_tag = "%s geometry=%s" % (geometry_tag, geometry)
     if style_precision is not None and not fold_latents:
         raise ValueError("style_precision needs fold_latents (the fp16mx style kernels take zs [K,32])")
     if renderer is None or not hasattr(ds, 'frame_batches'):
@@ -803,6 +847,7 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
     per_call = max(1, min(((1 << 31) - 1) // (styles * nt), (2 << 30) // (styles * nt * 12)))
     rgbs, ts, have = [], [], 0
     mode = {} if style_precision is None else {"style_precision": style_precision}
+    chain = {} if geometry is None else {"geometry": geometry}
     if geometry_cache is not None:
         os.makedirs(geometry_cache, exist_ok=True)
         min_weight = 0. if min_weight is None else float(min_weight)
@@ -833,12 +878,14 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
                 ro, rd = b['rays_o'][sl], b['rays_d'][sl]
                 cache = _cached_geometry(renderer, geometry_cache, 'geometry_%05d_%09d_%09d.pt' % (fid, p0, p1), key,
                                          lambda: renderer.build_geometry(ro, rd, args.N_samples, args.N_samples_fine, near=ds.near,
-                                                                         far=ds.far, jitter=jitter, min_weight=min_weight, key=key))
+                                                                         far=ds.far, jitter=jitter, min_weight=min_weight, key=key,
+                                                                         **chain))
                 out = renderer.restyle(cache, ro, rd, zs, key=key, n_coarse=args.N_samples, n_fine=args.N_samples_fine,
                                        **mode)
             else:
                 out = renderer.render_latents(b['rays_o'][sl], b['rays_d'][sl], args.N_samples, args.N_samples_fine,
-                                              near=ds.near, far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight, **mode)
+                                              near=ds.near, far=ds.far, jitter=jitter, zs=zs, min_weight=min_weight, **mode,
+                                              **chain)
             rgbs.append(out["rgb"].detach()), ts.append(out["t"].detach())
         have += R
         if have == res:           # a frame (this rank's part of it) is complete
@@ -856,7 +903,7 @@ def _render_style_shared(latents_model_1, dataloader, args, device, sv_path, ren
 def render_style(model_forward, samp_func, style_forward, concat_style_forward, latents_model_1, dataloader, args,
                  device, sv_path=None, model_forward_fine=None, samp_func_fine=None, sigma_scale=0., renderer=None,
                  share_geometry=False, min_weight=None, geometry_cache=None, geometry_tag=None, fold_latents=False,
-                 style_precision=None):
+                 style_precision=None, geometry=None):
     """reference rendering.py:93-239: stylised render of the `valid_style` rays; one
     style_%05d_fine_%05d.png + style_%05d_fine_depth_%05d.png pair per completed frame.
     Returns (rgb_map_fine, t_map_fine) = the rays left over after the last whole image, like the reference.
@@ -866,8 +913,11 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     geometry_cache (share_geometry only): a directory in which the ray-only half of every call is kept and reused, see
     _render_style_shared; geometry_tag: a string that goes into the cache keys (what the driver cannot see, e.g. the NeRF
     checkpoint step); fold_latents (share_geometry only): one latent per (style, frame), see _render_style_shared;
-    style_precision (share_geometry with fold_latents only): "fp16mx", see _render_style_shared."""
+    style_precision (share_geometry with fold_latents only): "fp16mx", see _render_style_shared;
+    geometry (share_geometry with a min_weight or a geometry_cache only): "chain", see _render_style_shared."""
     _require_fine(args)
+    if geometry is not None and not share_geometry:
+        raise ValueError("geometry needs share_geometry=True")
     if style_precision is not None and not (share_geometry and fold_latents):
         raise ValueError("style_precision needs share_geometry=True and fold_latents=True")
     if geometry_cache is not None and not share_geometry:
@@ -882,7 +932,7 @@ def render_style(model_forward, samp_func, style_forward, concat_style_forward, 
     if share_geometry:
         return _render_style_shared(latents_model_1, dataloader, args, device, sv_path, renderer, min_weight=min_weight,
                                     geometry_cache=geometry_cache, geometry_tag=geometry_tag, fold_latents=fold_latents,
-                                    style_precision=style_precision)
+                                    style_precision=style_precision, geometry=geometry)
     frame_num, h, w = ds.cps_valid.shape[0], ds.h, ds.w
     res = _local_res(ds, h * w)
     pend_rgb, pend_t, image_no = torch.zeros([0, 3], device=device), torch.zeros([0], device=device), 0

@@ -385,8 +385,8 @@ def train(args):
             dataset.mode = 'valid_style'
             rendering.render_style(dataloader=_Loader(dataset, batch_size), sv_path=out, share_geometry=args.share_geometry,
                                    geometry_cache=args.geometry_cache or None, geometry_tag="nerf_step=%d" % nerf_step,
-                                   fold_latents=args.fold_latents, style_precision=args.style_precision or None, **common,
-                                   **styled)
+                                   fold_latents=args.fold_latents, style_precision=args.style_precision or None,
+                                   geometry="chain" if args.chain_geometry else None, **common, **styled)
             print('Done, saving to', out)
             return out
         if args.render_train_style:
@@ -439,6 +439,13 @@ def main(argv=None):
             raise SystemExit("train_tgtcs: --style_precision fp16mx needs a --precision whose fine half is fp16mx, e.g. "
                              "fp16x3+fp16mx (got %s; the kernel runs the fine trunk and the style networks of a tile together)"
                              % args.precision)
+    if args.chain_geometry:
+        if not (args.render_valid_style and args.share_geometry):
+            raise SystemExit("train_tgtcs: --chain_geometry needs --render_valid_style --share_geometry (it is a geometry of the "
+                             "culled multi-latent render and of the geometry cache)")
+        if not (args.cull_weight >= 0 or args.geometry_cache):
+            raise SystemExit("train_tgtcs: --chain_geometry needs --cull_weight >= 0 or --geometry_cache (the dense multi-latent "
+                             "render has no chain geometry)")
     if args.origin_train and args.style_train:
         raise SystemExit("train_tgtcs: --origin_train and --style_train are two stages: one call each, in that order")
     for stage in ("origin_train", "style_train"):
