@@ -211,7 +211,12 @@ int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const d
  *   TGTC_CULL_OFF             always dense (and no statistic is taken).
  *   TGTC_CULL_ON              always two-phase.
  *   Every mode takes the dense pass where the list does not fit the dead planes (6 x R x n_coarse floats <
- *   R x (n_coarse + n_fine) x 4 + 8192 bytes), where R x (n_coarse + n_fine) >= 2^31, or for other precisions.
+ *   R x (n_coarse + n_fine) x 4 + 8192 bytes), where R x (n_coarse + n_fine) >= 2^31, or for a fine handle in
+ *   TGTC_PREC_FP16.
+ * A fine handle in TGTC_PREC_FP16X3 takes the two-phase pass under TGTC_CULL_ON ONLY (no break-even has chosen a threshold for
+ *   it: under AUTO and OFF its pass is dense, with the launches and counters it always had, and no statistic is taken).  Its
+ *   colour phase is tgtc_nerf_forward_list_x3 (below), its density launch tgtc_nerf_forward_rays(rgb = NULL); the compositor,
+ *   the bits and the accepted difference are those above.  No stash exists for it.
  * Statistic: the handle owns one pinned 8-byte host word.  Every chain render with it as the fine handle (AUTO and ON; in
  *   dense mode at the price of one run of the compaction's count kernel over sigma_f) ends with an asynchronous copy of
  *   (live count, R x (n_coarse + n_fine)) into it (none where the dead planes are smaller than the 8192-byte scratch).  AUTO reads the word without waiting for the device: a pipeline that
@@ -226,6 +231,17 @@ int tgtc_render_rays_plain(const tgtc_net* coarse, const tgtc_net* fine, const d
 int tgtc_net_set_cull(tgtc_net* net, int mode);
 float tgtc_net_live_fraction(const tgtc_net* net);
 long long tgtc_net_culled_renders(const tgtc_net* net);
+
+/* tgtc_nerf_forward_list for TGTC_PREC_FP16X3 handles: the full network (trunk, density head, base_remap, colour head) over a
+ * device-side list, the arithmetic of tgtc_nerf_forward_rays sample for sample (csrc/mlp_nerf_x3_list.hip: a persistent
+ * kernel, one workgroup per CU at most, 128 list slots per pass).  rgb[s] of the listed samples -- the bits
+ * tgtc_nerf_forward_rays(rgb, sigma) gives them -- and, where sigma is not NULL, sigma[s], the bits of
+ * tgtc_nerf_forward_rays(rgb = NULL); nothing else is touched.  List rules as tgtc_nerf_forward_list: n_live is a DEVICE
+ * pointer, *n_live == 0 writes nothing, a listed index >= R x N is not written.
+ * Any other precision, or R x N >= 2^31 -> TGTC_ERR_UNSUPPORTED.  Null pointers (sigma excepted), R < 0, N < 1 or a handle
+ * that is not a NeRF handle -> TGTC_ERR_ARG; R == 0 -> TGTC_OK without a launch. */
+int tgtc_nerf_forward_list_x3(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R,
+                              int N, const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, void* stream);
 
 /* The stash: the two-phase fine pass without the second trunk.  The list launch above runs layers 0-7 and the sigma head
  * again on samples the density launch has just finished; only base_remap and the colour head are new work.  With a STASH
@@ -276,7 +292,9 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  *   fine pass:   a fine handle in fp16mx with a screen; density AND colour of the candidates from
  *                tgtc_nerf_forward_list_sigma, the compositor of the two-phase pass.  List + scratch live where the
  *                two-phase pass keeps its list; no stash is used.  Counts in tgtc_net_culled_renders; TGTC_CULL_OFF on the
- *                handle switches it off as well.
+ *                handle switches it off as well.  A fine handle in fp16x3 with a screen is screened the same way under
+ *                TGTC_CULL_ON only (the candidates from tgtc_nerf_forward_list_x3 with sigma; AUTO is pass 3 of
+ *                tgtc_screen_auto_decision); under TGTC_CULL_AUTO / OFF its screen has no part in a plain render.
  * tgtc_render_workspace_bytes is what it was; there is no host synchronisation in a render.
  * tgtc_net_enable_screen(net, stream): packs the fp16 form and calibrates the margin -- screen and exact sigma-only launches
  *   on 256 fixed host-generated rays (each between two points uniform in the box) x 128 depths equally spaced on [0, 1]: the
@@ -296,7 +314,7 @@ int tgtc_nerf_stash_heads(const tgtc_net* net, const double* rays_o, const doubl
  * tgtc_net_screened_renders: how many chain renders screened their pass with this handle (-1 for NULL / no screen state).
  * tgtc_screen_list_fits / tgtc_screen_auto_decision: the two rules as pure host functions -- does a list of up to M indices
  *   and the 8192-byte scratch fit `bytes`; does AUTO screen pass 0 (coarse) / 1 (fine) / 2 (the sigma-only fine pass of the
- *   chain geometry, below) on a landed (candidates, total).
+ *   chain geometry, below) / 3 (the two-phase fine pass of a fine handle in fp16x3) on a landed (candidates, total).
  * The launches as entries of their own (tests, tools):
  *   tgtc_nerf_screen_rays: sigma [R,N] from the screen form (TGTC_ERR_UNSUPPORTED without a screen): NaN for exactly the
  *     samples outside the box or not finite, and for the others the bits of the sigma-only launch of a TGTC_PREC_FP16 handle

@@ -48,6 +48,7 @@ EXTRA = {
     "fold_latents": (None, False),     # --share_geometry with --cull_weight or --geometry_cache: one latent per (style, frame) (HELP below)
     "style_precision": (str, ""),      # --fold_latents with a fine network in fp16mx: "fp16mx" runs the style networks in fp16mx (HELP below)
     "chain_geometry": (None, False),   # --share_geometry with --cull_weight or --geometry_cache: the plain chain's screened passes (HELP below)
+    "two_phase": (None, False),        # --render_valid / --render_train: the chain with the two-phase fine pass (HELP below)
     "latent_seed": (int, -1),          # seed of the latent draw when the table is initialised from the VAE (-1: unseeded, like
                                        # the reference); under torchrun rank 0 draws and broadcasts either way
     "origin_train": (None, False),     # run the reference's Origin_train loop on the HIP training kernels (HELP below)
@@ -127,6 +128,13 @@ HELP = {
                       "screened or not, the images are the same bits.  Against a run without the flag the fine depths "
                       "differ by the rounding between two coarse kernels, so the cache keys carry geometry=chain and a "
                       "--geometry_cache directory never serves one run's files to the other.  Default: off",
+    "two_phase": "with --render_valid or --render_train (refused with a --render_*_style flag, --origin_train or "
+                 "--style_train): render on the chain of per-sample kernels with the two-phase fine pass forced on -- "
+                 "densities of every fine sample first (behind the density screen where the library's rule says it pays), "
+                 "then the full fine network on the samples that carry density only.  For a --precision whose fine half is "
+                 "fp16x3 (the default) this is the only way to that pass; for fp16mx the library's own policy reaches it "
+                 "too.  The image files are byte-identical to a run on the dense chain; against the default run (the ray "
+                 "kernel) they differ by the rounding between the chain and the ray kernel.  Default: off",
 }
 
 

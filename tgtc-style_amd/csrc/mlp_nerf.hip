@@ -309,6 +309,18 @@ int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const doub
     return nerf_mx_launch(IN_LIST, true, a, st);
 }
 
+// The same for fp16x3 handles (mlp_nerf_x3_list.hip): the bits of the dense full launch at the listed samples
+// (the caller has checked the precision and R x N < 2^31)
+int nerf_forward_list_x3_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                              const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st) {
+    NerfArgs a{};
+    a.M = R * (int64_t)N, a.N = N, a.rays_o = rays_o, a.rays_d = rays_d, a.ts = ts, a.rgb = rgb, a.sigma = sigma;
+    a.live = live, a.n_live = n_live;
+    a.bias = net->dev;
+    a.stream = net->dev + net->bias_bytes;
+    return nerf_x3_list_launch(a, st);
+}
+
 // sigma[live[i]] for the *n_live samples of a device-side list, fp16x3 handles: the bits of the sigma-only launch over rays
 // (the caller has checked the precision and R x N < 2^31)
 int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
@@ -773,5 +785,18 @@ extern "C" int tgtc_nerf_forward_list_sigma(const tgtc_net* net, const double* r
     if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
         return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list_sigma: R x N >= 2^31 (chunk the rays)");
     return nerf_forward_list_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, sigma, as_stream(stream));
+}
+
+extern "C" int tgtc_nerf_forward_list_x3(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts,
+                                         int64_t R, int N, const uint32_t* live, const uint32_t* n_live, float* rgb,
+                                         float* sigma, void* stream) {
+    TGTC_REQUIRE(net && net->kind == 0 && R >= 0 && N >= 1, "nerf_forward_list_x3: bad argument");
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(rays_o && rays_d && ts && live && n_live && rgb, "nerf_forward_list_x3: null pointer");
+    if (net->precision != TGTC_PREC_FP16X3)
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list_x3: built for fp16x3 handles only (got precision %d)", net->precision);
+    if (R >= ((int64_t)1 << 31) || R * (int64_t)N >= ((int64_t)1 << 31))
+        return fail(TGTC_ERR_UNSUPPORTED, "nerf_forward_list_x3: R x N >= 2^31 (chunk the rays)");
+    return nerf_forward_list_x3_impl(net, rays_o, rays_d, ts, R, N, live, n_live, rgb, sigma, as_stream(stream));
 }
 #endif  // TGTC_TU_FP16_ONLY

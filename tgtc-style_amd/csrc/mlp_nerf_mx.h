@@ -40,6 +40,9 @@ int nerf_mx2_heads_launch(const NerfArgs& a, const NerfStashArgs& s, hipStream_t
 int nerf_x3s_launch(const NerfArgs& a, hipStream_t st);
 // the same over a device-side list (a.live, a.n_live): sigma[live[slot]], nothing else
 int nerf_x3s_list_launch(const NerfArgs& a, hipStream_t st);
+// fp16x3, the FULL network over a device-side list (a.live, a.n_live): rgb[live[slot]] and, where a.sigma is given,
+// sigma[live[slot]] -- the bits of the dense full launch; one column tile per wave, persistent (mlp_nerf_x3_list.hip)
+int nerf_x3_list_launch(const NerfArgs& a, hipStream_t st);
 // fp16 (one product), rays in, sigma out (the density screen): four column tiles per wave, one wave per SIMD, persistent
 // (mlp_nerf_fp16s.hip); a.bias / a.stream are a handle's TGTC_PREC_FP16 form
 // The screen's declared domain (DESIGN 3.1 "The screen's domain"): a sample with a coordinate outside |p| <= kScreenBox, or not

@@ -39,6 +39,8 @@ int launch_count_live(const float* w, int64_t M, float min_weight, uint32_t* scr
 int launch_live_stat(uint32_t* scratch, int64_t M, const uint32_t** stat, hipStream_t st);
 int nerf_forward_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                            const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st);
+int nerf_forward_list_x3_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
+                              const uint32_t* live, const uint32_t* n_live, float* rgb, float* sigma, hipStream_t st);
 int nerf_sigma_list_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
                          const uint32_t* live, const uint32_t* n_live, float* sigma, hipStream_t st);
 int nerf_sigma_list_mx_impl(const tgtc_net* net, const double* rays_o, const double* rays_d, const float* ts, int64_t R, int N,
@@ -366,6 +368,17 @@ constexpr float kScreenFineThreshold = 0.45f;
 // The precisions differ; pass 2 keeps the smaller threshold for both.  It clears the orbit's share (0.143) by a wide margin:
 // AUTO screens the sigma-only fine pass of the benchmark's frames once a share has landed.
 constexpr float kScreenFineSigmaThreshold = 0.51f;
+// Pass 3, the two-phase fine pass of a fine handle in fp16x3 (fine_pass below, TGTC_CULL_ON only): the screen
+// launch plus C x the FULL fp16x3 list launch (nerf_x3_list_kernel, density and colour) against the dense full launch c,
+// C* = (c - p) / l, by the same recipe.  Measured on the MI355X (tools/time_plain_x3.py --step0,
+// profiles/plain_x3_two_phase_timing.json "step0") on the fine depths of a real 400 x 400 render (pose 0) at 128 + 64, both
+// handles in fp16x3:
+//   p = 18.92 ms, c = 73.43 ms, the full list launch 2.460 ns per listed sample (l = 75.58 ms): C* = (c - p) / l = 0.721.
+//   Candidate share over the orbit (spiral_pose 0 .. 119) 0.112 .. 0.142, spread 0.030; the extra launches (compaction, two
+//   statistics) 0.3 ms of l, 0.005.  0.721 - 0.030 - 0.005 = 0.68.
+// (The unscreened form, for the record: the dense sigma-only launch s = 58.77 ms, so L* = (c - s) / l = 0.196 on the live share,
+// 0.098 .. 0.127 over the orbit.  No AUTO rule is built on it: the pass runs under TGTC_CULL_ON only.)
+constexpr float kScreenFineX3Threshold = 0.68f;
 
 static bool screen_enabled(const tgtc_net* net) { return net->screen && net->screen->dev && net->screen->landed; }
 
@@ -375,9 +388,12 @@ extern "C" int tgtc_screen_list_fits(size_t bytes, int64_t M) {
 }
 
 // AUTO's rule, pure host code: screen iff a share has landed and lies below the threshold of the pass (0: coarse, 1: fine,
-// 2: the sigma-only fine pass of the chain geometry)
+// 2: the sigma-only fine pass of the chain geometry, 3: the two-phase fine pass of a fine handle in fp16x3)
 extern "C" int tgtc_screen_auto_decision(int pass, uint32_t candidates, uint32_t total) {
-    const float thr = pass == 0 ? kScreenCoarseThreshold : pass == 2 ? kScreenFineSigmaThreshold : kScreenFineThreshold;
+    const float thr = pass == 0   ? kScreenCoarseThreshold
+                      : pass == 2 ? kScreenFineSigmaThreshold
+                      : pass == 3 ? kScreenFineX3Threshold
+                                  : kScreenFineThreshold;
     return total != 0 && candidates <= total && (double)candidates < (double)thr * (double)total;
 }
 
@@ -440,12 +456,17 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
     char* const dead = reinterpret_cast<char*>(ws.ts_c);
     const size_t dead_bytes = (size_t)(reinterpret_cast<char*>(ws.ts_f) - dead);
     tgtc_cull_state* const c = fine->cull;
-    const bool listable = c && fine->precision == TGTC_PREC_FP16_FP6 && M < ((int64_t)1 << 31);
+    // a fine handle in fp16x3 takes the two-phase family only where the caller asks for it (TGTC_CULL_ON): no break-even
+    // against its dense pass has chosen a threshold for AUTO, under which (as under OFF) the pass is what it always was
+    const bool x3 = c && fine->precision == TGTC_PREC_FP16X3 && c->mode == TGTC_CULL_ON;
+    const bool listable = c && (fine->precision == TGTC_PREC_FP16_FP6 || x3) && M < ((int64_t)1 << 31);
     const bool fits = listable && tgtc_screen_list_fits(dead_bytes, M);
     // the screen belongs to the two-phase family: TGTC_CULL_OFF switches it off with the rest
     tgtc_screen_state* const sc = listable && c->mode != TGTC_CULL_OFF && screen_enabled(fine) ? fine->screen : nullptr;
-    const bool screen = sc && fits && screen_wanted(sc, 1);
+    const bool screen = sc && fits && screen_wanted(sc, x3 ? 3 : 1);
     const bool cull = screen || (fits && cull_wanted(c));
+    // the full network over a list, in the handle's precision (fp16x3 carries no stash: tgtc_net_set_stash refuses it)
+    const auto list_launch = x3 ? nerf_forward_list_x3_impl : nerf_forward_list_impl;
     uint32_t* scratch = nullptr;
     int rc;
     if (screen) {
@@ -458,7 +479,7 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         if (rc) return rc;
         rc = launch_compact_candidates(ws.sigma_f, M, sc->margin, live, scratch, st);
         if (rc) return rc;
-        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, ws.sigma_f, st);
+        rc = list_launch(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, ws.sigma_f, st);
         if (rc) return rc;
         ++c->culled, ++sc->screened;
     } else if (cull && fine->stash) {
@@ -481,7 +502,7 @@ static int fine_pass(const tgtc_net* fine, const double* rays_o, const double* r
         if (rc) return rc;
         rc = launch_compact_live(ws.sigma_f, M, 0.0f, live, scratch, nullptr, st);
         if (rc) return rc;
-        rc = nerf_forward_list_impl(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, nullptr, st);
+        rc = list_launch(fine, rays_o, rays_d, ws.ts_f, R, nt, live, scratch, ws.rgb_f, nullptr, st);
         if (rc) return rc;
         ++c->culled;
     } else {

@@ -62,6 +62,8 @@ _SIGNATURES = {
     "tgtc_nerf_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_forward_rays": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
     "tgtc_nerf_forward_list": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tgtc_nerf_forward_list_x3": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p],
     "tgtc_net_set_cull": [c_void_p, c_int],
     "tgtc_net_live_fraction": [c_void_p],
     "tgtc_net_culled_renders": [c_void_p],
@@ -332,6 +334,16 @@ def nerf_create(state, precision="fp16x3", prefix="net."):
     check(lib.tgtc_nerf_create(arr, len(pairs), PRECISIONS[precision], ctypes.byref(h)))
     del keep
     return Net(h, precision)
+
+
+def nerf_forward_list_x3(net, rays_o, rays_d, ts, live, n_live, rgb, sigma=None):
+    """tgtc_nerf_forward_list_x3: the full fp16x3 network of `net` (a Net) over the device-side list live[: *n_live] of the
+    [R, N] grid ts -- rgb [R*N,3] (and sigma [R*N] where given) are written at the listed samples only.  n_live is a device
+    tensor of one int32; nothing is synchronised.  RuntimeError for a handle in another precision."""
+    require_gpu(rays_o, rays_d, ts, live, n_live, rgb, sigma)
+    R, N = ts.shape
+    check(load().tgtc_nerf_forward_list_x3(net.handle, ptr(rays_o), ptr(rays_d), ptr(ts), R, N, ptr(live), ptr(n_live), ptr(rgb),
+                                           ptr(sigma), stream()))
 
 
 def style_create(concat_state=None, style_state=None, precision="fp16x3"):

@@ -151,7 +151,10 @@ class RayRenderer:
         densities first and the colour head on the live samples only once the fine handle has seen a low enough live
         share), True / False force it on / off.  The mode lives on the FINE HANDLE and is set by every plain render of
         this renderer; the images are the same bits either way (include/tgtc_hip.h).
-        stash (the same renders): None attaches the stash of the two-phase pass as STASH_DEFAULT says, True / False force it,
+        A fine handle in fp16x3 takes the two-phase pass with cull=True only, and on the chain only (fused=False: fused=True
+        resolves fp16x3+fp16x3 to the ray kernel, which has no such pass): the density-only launch, then the full fp16x3
+        network over the list of live samples (tgtc_nerf_forward_list_x3).  None and False leave its pass dense, as it was.
+        stash (fine fp16mx only): None attaches the stash of the two-phase pass as STASH_DEFAULT says, True / False force it,
         a uint8 device tensor is attached as it is (any size from one slot per region up is correct);
         it is allocated at the first such render, STASH_SHARE x 932 bytes per fine sample (about 4 GB for 400 x 400 rays at
         128 + 64), and never with cull=False.  The same bits again.
@@ -159,7 +162,9 @@ class RayRenderer:
         -- fp16 densities of all samples first, the exact kernels on the candidates only.  None enables the screen on both
         handles at the first such render (one host synchronisation per handle) and leaves the decision to the library
         (TGTC_SCREEN_AUTO), True forces it wherever it fits, False switches it off; one value for both passes, or a pair
-        (coarse, fine).  cull=False switches the fine screen off as well.  The same bits again: measured for samples inside the
+        (coarse, fine).  cull=False switches the fine screen off as well.  With cull=True the fine screen covers a fine handle
+        in fp16x3 too (enabled at the first such render; under cull=None / False that handle's plain render has no screen).
+        The same bits again: measured for samples inside the
         screen's box |x|, |y|, |z| <= 2, where its margin is calibrated; a sample outside it is always handed to the exact
         kernel, so near / far beyond NDC cost time, not bits (DESIGN 3.1 "The screen's domain").
         The culled stylised calls and build_geometry use `screen` only under geometry="chain" (DESIGN 3.1i): there the fine
@@ -191,9 +196,10 @@ class RayRenderer:
         """Put this renderer's `screen` on the two handles, enabling the screen where a pass may be screened (host calls;
         handles are repacked when weights change).  Handles in fp16 have no screen.
         chain: the call is a chain geometry (geometry="chain"), whose sigma-only fine pass is screened for a fine handle in
-        fp16x3 as well; plain renders screen a fine handle in fp16mx only."""
+        fp16x3 as well; plain renders screen a fine handle in fp16mx, and one in fp16x3 where cull is True (its two-phase
+        pass exists under TGTC_CULL_ON only)."""
         pair = self.screen if isinstance(self.screen, tuple) else (self.screen, self.screen)
-        fine_precs = ("fp16mx", "fp16x3") if chain else ("fp16mx",)
+        fine_precs = ("fp16mx", "fp16x3") if chain or self.cull is True else ("fp16mx",)
         for net, want, precs in ((self.coarse.packed(), pair[0], ("fp16x3",)), (self.fine.packed(), pair[1], fine_precs)):
             if net.precision not in precs:
                 continue

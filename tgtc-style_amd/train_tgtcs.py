@@ -398,8 +398,10 @@ def train(args):
         if args.render_valid or args.render_train:
             out = os.path.join(sv_path, 'nerf_gen_data2')
             dataset.mode = 'train' if args.render_train else 'valid'
-            rendering.cal_geometry(dataloader=_Loader(dataset, batch_size), sv_path=out,
-                                   renderer=rendering.RayRenderer(model, model_fine), **common)
+            # --two_phase: the chain with the two-phase fine pass forced on (the dense chain's bytes); default: the fastest path
+            plain = (rendering.RayRenderer(model, model_fine, fused=False, cull=True) if args.two_phase
+                     else rendering.RayRenderer(model, model_fine))
+            rendering.cal_geometry(dataloader=_Loader(dataset, batch_size), sv_path=out, renderer=plain, **common)
             print('Done, saving to', out)
             return out
     raise SystemExit("train_tgtcs: nothing to do -- pass --render_valid_style, --render_train_style, --render_valid, "
@@ -446,6 +448,12 @@ def main(argv=None):
         if not (args.cull_weight >= 0 or args.geometry_cache):
             raise SystemExit("train_tgtcs: --chain_geometry needs --cull_weight >= 0 or --geometry_cache (the dense multi-latent "
                              "render has no chain geometry)")
+    if args.two_phase:
+        others = [f for f in ("render_valid_style", "render_train_style", "origin_train", "style_train") if getattr(args, f)]
+        if others or not (args.render_valid or args.render_train):
+            raise SystemExit("train_tgtcs: --two_phase needs --render_valid or --render_train and nothing else (it is the fine "
+                             "pass of the plain render on the chain%s)"
+                             % ("; it does not go with --" + " / --".join(others) if others else ""))
     if args.origin_train and args.style_train:
         raise SystemExit("train_tgtcs: --origin_train and --style_train are two stages: one call each, in that order")
     for stage in ("origin_train", "style_train"):
