@@ -42,6 +42,29 @@ int tgtc_trainer_status(tgtc_trainer* trainer, void* stream);
  * read it at the reference's i_print cadence, train_tgtcs.py:257-266, not per iteration). */
 int tgtc_trainer_overflows(tgtc_trainer* trainer, void* stream, unsigned* count);
 
+/* Sparse backward: most samples of a NeRF training batch carry an upstream gradient that is exactly zero (a sample with
+ * sigma + noise <= 0 has alpha = 0: its compositing weight, and with it d_rgb and d_sigma, are +-0), and such a sample adds
+ * exactly nothing to any gradient.  In TGTC_TRAIN_SPARSE mode tgtc_trainer_backward first builds, on the device, the
+ * ascending list of the LIVE samples -- sample m is live iff not all of d_sigma[m], d_rgb[m, 0..2] compare == 0.0f: -0.0 is
+ * dead, NaN and inf are live, so the overflow guard still sees them -- and runs the input-gradient chain and the weight
+ * gradients over that list alone.  The gradients are those of the dense backward up to fp32 / fp16x3 rounding, not the
+ * same bits (the 16-sample tiles are composed of other samples, and the chain's per-tile scales follow the tile maximum).
+ * No host synchronisation: the host never learns the count, the grids are those of M samples.  The forward is untouched.
+ * The mode is the caller's and is never chosen or changed by the library: TGTC_TRAIN_DENSE is the default, and a sparse
+ * backward whose workspace is below tgtc_trainer_workspace_bytes_sparse(M) returns TGTC_ERR_ARG with nothing launched -- it
+ * does not run dense instead.  The forward and the dense backward take a workspace of either size.
+ *   tgtc_trainer_set_sparse                TGTC_ERR_ARG for a NULL trainer or any other mode
+ *   tgtc_trainer_workspace_bytes_sparse    the dense size + the list (uint32 [M_pad]), its count and the compaction's partial
+ *                                          counts; 0 for M <= 0
+ *   tgtc_trainer_live_counts               *live / *total = live samples / all samples, summed over the SPARSE backwards since
+ *                                          trainer_create (dense backwards add nothing); synchronises `stream` like
+ *                                          tgtc_trainer_overflows: read it at the i_print cadence */
+#define TGTC_TRAIN_DENSE 0
+#define TGTC_TRAIN_SPARSE 1
+int tgtc_trainer_set_sparse(tgtc_trainer* trainer, int mode);
+size_t tgtc_trainer_workspace_bytes_sparse(int64_t M);
+int tgtc_trainer_live_counts(tgtc_trainer* trainer, void* stream, unsigned long long* live, unsigned long long* total);
+
 /* Workspace: about 20 KB per sample -- two fp16 planes of 2 528 activations, 2 448 fp32 pre-activation gradients, one
  * 64-bit gate word per gated layer, 16-sample tile and lane -- e.g. 2.6 GB at M = 131 072 (1 024 rays x 128 samples of the
  * fine network).  It belongs to ONE forward / backward pair: a second forward before the backward of the first needs its

@@ -54,6 +54,7 @@ EXTRA = {
     "origin_train": (None, False),     # run the reference's Origin_train loop on the HIP training kernels (HELP below)
     "train_seed": (int, 0),            # --origin_train: seed of the initial weights, the batches and the draws (HELP below)
     "train_unfused": (None, False),    # --origin_train: train on the per-layer path, the cross-check of the fused kernels
+    "train_sparse": (None, False),     # --origin_train: the sparse backward of the fused training kernels (HELP below)
     "style_train": (None, False),      # run the reference's Style_train loop: style MLPs and latent table (HELP below)
     "coh_until": (int, 122000),        # --style_train: last step with the coherence term in the style optimiser's loss
     "latent_lrate": (float, 1e-3),     # --style_train: learning rate of the latent table's own Adam
@@ -73,6 +74,11 @@ HELP = {
                   "continues the interrupted one.  -1: unseeded, like the reference.  Default 0",
     "train_unfused": "with --origin_train: differentiable per-layer HIP dense layers in place of the fused training "
                      "kernels (same arithmetic, one launch per product); the cross-check",
+    "train_sparse": "with --origin_train: run the backward of the fused training kernels over the samples whose upstream "
+                    "gradient is not exactly zero (a sample with sigma + noise <= 0 has compositing weight 0 and adds "
+                    "nothing to any gradient).  Same gradients up to fp32 / fp16x3 rounding; the [ORIGIN TRAIN] line also "
+                    "carries the live share of each network since the previous line.  Never switched on by itself.  Refused "
+                    "together with --train_unfused, --style_train (its NeRF pair is frozen) and any --render_* flag",
     "style_train": "train the two style MLPs and the latent table on the frozen NeRF pair (the reference's Style_train, "
                    "steps up to --total_step inclusive).  NeRF weights from the newest NNNNNN.tar, style MLPs from the "
                    "newest style_*.tar or freshly initialised, latents from the newest latent_*.tar, else the VAE, else "

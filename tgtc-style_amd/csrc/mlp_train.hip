@@ -277,6 +277,7 @@ struct tgtc_trainer {
     size_t fwd_map_off = 0, fwd_bias_map_off = 0, bwd_map_off = 0, fwd_stream_off = 0, bwd_stream_off = 0, unperm_off = 0, maxima_off = 0;
     int fwd_slots = 0, bwd_slots = 0;   // fragment slots (fragments * 512) incl. chunk padding
     size_t fwd_stream_bytes = 0, bwd_stream_bytes = 0;
+    int sparse = TGTC_TRAIN_DENSE;      // tgtc_trainer_set_sparse
 };
 
 namespace tgtc {
@@ -285,7 +286,11 @@ namespace train {
 struct WsLayout {
     long long m_pad, n_tiles;
     size_t h_hi, h_lo, dz, gates, total;
+    // behind the dense layout (tgtc_trainer_workspace_bytes_sparse): the live list uint32 [M_pad], its count, the partial
+    // counts of the compaction
+    size_t list, count, parts, total_sparse;
 };
+constexpr size_t kLivePartsBytes = 1024 * sizeof(unsigned);
 static WsLayout ws_layout(long long M) {
     WsLayout w;
     w.m_pad = (M + kTileSamples - 1) / kTileSamples * kTileSamples;
@@ -301,6 +306,10 @@ static WsLayout ws_layout(long long M) {
     w.dz = take((size_t)w.m_pad * Z_COLS * sizeof(float));
     w.gates = take((size_t)kGateLayers * w.n_tiles * 64 * sizeof(unsigned long long));
     w.total = off;
+    w.list = take((size_t)w.m_pad * sizeof(unsigned));
+    w.count = take(sizeof(unsigned));
+    w.parts = take(kLivePartsBytes);
+    w.total_sparse = off;
     return w;
 }
 
@@ -413,168 +422,23 @@ __device__ __forceinline__ void dgrad_epi(const float4v& acc, unsigned long long
     }
 }
 
-__global__ void __launch_bounds__(CfgT::NWAVES * 64, 2) train_dgrad_kernel(BwdArgs a) {
-    using C = CfgT;
-    __shared__ __attribute__((aligned(16))) char smem[C::RING_BYTES + kNerfBiasBytes];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane >> 4, n = lane & 15;
-    const long long tile = (long long)blockIdx.x * C::NWAVES + wave;
-    const long long s = tile * 16 + n;
-    const bool live = s < a.M;
+// The live list of a sparse backward (tgtc_trainer_set_sparse): ascending indices of the samples whose upstream gradient is
+// not all zero, and how many there are -- both on the device, the host never learns the count.
+struct LiveList {
+    const unsigned* list;    // [count] valid entries of [M_pad]
+    const unsigned* count;   // [1]
+};
 
-    // ---- ordinary loads first: the ten gate words of this lane, the head gradients of its sample
-    unsigned long long gw[kGateLayers];
-#pragma unroll
-    for (int l = 0; l < kGateLayers; ++l) gw[l] = a.gates[((size_t)l * a.n_tiles + tile) * 64 + lane];
-    float hd[4] = {0.f, 0.f, 0.f, 0.f};   // [d sigma, dz_r, dz_g, dz_b] (rgb = sigmoid(z): dz = d rgb * rgb * (1 - rgb), models.py:111)
-    if (live) {
-        hd[0] = a.d_sigma[s];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float y = a.rgb[s * 3 + k];
-            hd[1 + k] = a.d_rgb[s * 3 + k] * y * (1.0f - y);
-        }
-    }
-#pragma unroll
-    for (int l = 0; l < kGateLayers; ++l) asm volatile("" : "+v"(gw[l]));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(hd[k]));
-
-    WeightStream<C, SingleStreamMap<kDgradFrags>> ws;
-    const char* const streams[1] = {a.stream};
-    ws.init(streams, smem, wave, lane);
-#pragma unroll
-    for (int j = 0; j < kNerfBiasBytes / (C::NWAVES * 1024); ++j)
-        lds_dma16(a.zero_bias + (j * C::NWAVES + wave) * 1024 + lane * 16, smem + C::RING_BYTES + (j * C::NWAVES + wave) * 1024);
-    ws.prologue();
-
-    const long long m_pad = a.n_tiles * 16;               // rows up to M_pad exist; dead samples carry zeros
-    auto seg_row = [&](int col0, int width) { return a.dz + seg_at(col0, width, m_pad, s); };
-    // heads: true values to the stash (16 floats: [d sigma, dz rgb, 0 ...]), tile maximum -> first scale
-    *reinterpret_cast<float4v*>(seg_row(Z_HEADS, 16) + 4 * g) = g == 0 ? float4v{hd[0], hd[1], hd[2], hd[3]} : float4v{0.f, 0.f, 0.f, 0.f};
-    // segment maxima of this wave's tile: kept (wave-uniform) until the chain is through and published then -- an atomic is
-    // a vector-memory operation, and one per layer in front of the ring's counted waits stalled every layer's first chunks
-    unsigned seg_max[12];
-    // The two heads carry their own scales (and their own segment maxima, 10: colour, 11: sigma): d sigma and dz_rgb may be
-    // orders of magnitude apart (compositing gives |d sigma| ~ 1e-3 |d rgb| early in training and the reverse is as legal),
-    // and the smaller one at the larger one's scale loses its low bits to fp16.  The colour head's values enter at D0, the
-    // sigma row at D2 -- two layers after the colour branch has shrunk its values and the lagged scale has grown: no scale up to
-    // and including D2's outputs may exceed the one d sigma fits in, or d sigma (and the products it feeds) leave the fp16
-    // range: hi = inf, lo = x - inf, and the layer sums to NaN without any inf left for the maxima to show (round 4).
-    const float m_sig = wave_max(fabsf(hd[0]));
-    float m = wave_max(fmaxf(fabsf(hd[1]), fmaxf(fabsf(hd[2]), fabsf(hd[3]))));
-    seg_max[10] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, m));
-    seg_max[11] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, m_sig));
-    const int e_sig = scale_exp(m_sig, 100);   // (no sigma gradient in this tile: no constraint)
-    int e_in = scale_exp(m, e_sig);            // (no colour gradient: the branch carries zeros, at the scale sigma will need)
-    // natural order k = 8g + j: the four values sit in lane group 0; SIGMA: the sigma entry alone (D2), else the colour entries (D0)
-    auto heads_frag = [&](auto sigma_, int e, half8& h, half8& l) {
-        constexpr bool SIGMA = decltype(sigma_)::value;
-        const float sc = pow2f(e);
-        unsigned h01 = 0, l01 = 0, h23 = 0, l23 = 0;
-        if (g == 0) {
-            split_pair_signed(SIGMA ? hd[0] * sc : 0.f, SIGMA ? 0.f : hd[1] * sc, h01, l01);
-            split_pair_signed(SIGMA ? 0.f : hd[2] * sc, SIGMA ? 0.f : hd[3] * sc, h23, l23);
-        }
-        h = __builtin_bit_cast(half8, u4{h01, h23, 0u, 0u});
-        l = __builtin_bit_cast(half8, u4{l01, l23, 0u, 0u});
-    };
-
-    const lds_cptr bias_lane = opaque((lds_cptr)smem + C::RING_BYTES + 16 * g);
-    ws.start();
-
-    half8 Xh[8][1], Xl[8][1], Yh[8][1], Yl[8][1];
-    float pend[2];
-    // after a layer: the tile maximum of its gated outputs fixes the scale of the layer AFTER the next (the next layer's
-    // operands were already produced at the scale derived one layer earlier); segment maxima feed the weight-gradient kernel
-    auto close = [&](auto seg_, float& mm, int cur, int keep) {   // cur: the scale in force, keep: the answer for an all-zero tile
-        const float t = wave_max(mm);
-        seg_max[decltype(seg_)::value] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, t));
-#ifdef TGTC_DGRAD_ATOMIC_PER_LAYER   // A/B build: the round's first form, one atomic per layer in front of the ring waits
-        if (lane == 0) atomicMax(a.maxima + decltype(seg_)::value, __builtin_bit_cast(unsigned, t));
-#endif
-        mm = 0.f;
-        return max(cur - 120, min(cur + 120, scale_exp(t, keep)));   // (s_op = 2^(difference of consecutive scales) stays a normal float)
-    };
-
-    // D0: rgb_layers.1^T.  inputs heads (scale e_in), outputs dz_f at the same scale (|W| < 1: the values shrink)
-    int e_out = e_in, e_next;
-    {
-        half8 Bh[1][1], Bl[1][1];
-        heads_frag(std::false_type{}, e_in, Bh[0][0], Bl[0][0]);
-        half8 Zh[4][1], Zl[4][1];
-        m = 0.f;
-        {
-            const float s_true = pow2f(-e_in), s_op = pow2f(e_out - e_in);
-            float* const zrow = seg_row(Z_F, 128);
-            dense_layer<C, dgrad_frag0(0), 1, 8, 0>(ws, bias_lane, Bh, Bl, [&](auto rt_, auto, auto h_, const float4v& acc) {
-                constexpr int rt = decltype(rt_)::value, hf = decltype(h_)::value;
-                dgrad_epi<rt, hf, true>(acc, gw[9], s_true, s_op, m, pend, zrow, g, Zh[rt / 2][0], Zl[rt / 2][0]);
-            });
-        }
-        e_next = min(close(ic<9>{}, m, e_out, e_sig), e_sig);
-        // D1: rgb_layers.0^T (activation columns): dz_f -> dz_remap
-        e_in = e_out, e_out = e_next;
-        {
-            const float s_true = pow2f(-e_in), s_op = pow2f(e_out - e_in);
-            float* const zrow = seg_row(Z_REMAP, 256);
-            dense_layer<C, dgrad_frag0(1), 4, 16, 0>(ws, bias_lane, Zh, Zl, [&](auto rt_, auto, auto h_, const float4v& acc) {
-                constexpr int rt = decltype(rt_)::value, hf = decltype(h_)::value;
-                dgrad_epi<rt, hf, true>(acc, gw[8], s_true, s_op, m, pend, zrow, g, Yh[rt / 2][0], Yl[rt / 2][0]);
-            });
-        }
-        e_next = min(close(ic<8>{}, m, e_out, e_sig), e_sig);
-    }
-    // D2: [base_remap^T | sigma^T]: [dz_remap | heads] -> dz_7
-    e_in = e_out, e_out = e_next;
-    {
-        half8 Bh[9][1], Bl[9][1];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) Bh[k][0] = Yh[k][0], Bl[k][0] = Yl[k][0];
-        heads_frag(std::true_type{}, e_in, Bh[8][0], Bl[8][0]);
-        const float s_true = pow2f(-e_in), s_op = pow2f(e_out - e_in);
-        float* const zrow = seg_row(z_layer(7), 256);
-        dense_layer<C, dgrad_frag0(2), 9, 16, 0>(ws, bias_lane, Bh, Bl, [&](auto rt_, auto, auto h_, const float4v& acc) {
-            constexpr int rt = decltype(rt_)::value, hf = decltype(h_)::value;
-            dgrad_epi<rt, hf, true>(acc, gw[7], s_true, s_op, m, pend, zrow, g, Xh[rt / 2][0], Xl[rt / 2][0]);
-        });
-    }
-    e_next = close(ic<7>{}, m, e_out, e_out);
-    // D3..D9: base_layers[7..1]^T: dz_l -> dz_{l-1}
-    auto hidden = [&](auto d_, auto last_, const half8 (&Ih)[8][1], const half8 (&Il)[8][1], half8 (&Oh)[8][1], half8 (&Ol)[8][1]) {
-        constexpr int d = decltype(d_)::value, l_out = 9 - d;          // D3 -> dz_6 ... D9 -> dz_0
-        constexpr bool last = decltype(last_)::value;
-        e_in = e_out, e_out = e_next;
-        const float s_true = pow2f(-e_in), s_op = pow2f(e_out - e_in);
-        float* const zrow = seg_row(z_layer(l_out), 256);
-        dense_layer<C, dgrad_frag0(d), 8, 16, 0>(ws, bias_lane, Ih, Il, [&](auto rt_, auto, auto h_, const float4v& acc) {
-            constexpr int rt = decltype(rt_)::value, hf = decltype(h_)::value;
-            dgrad_epi<rt, hf, !last>(acc, gw[l_out], s_true, s_op, m, pend, zrow, g, Oh[rt / 2][0], Ol[rt / 2][0]);
-        });
-        e_next = close(ic<l_out>{}, m, e_out, e_out);
-    };
-    hidden(ic<3>{}, std::false_type{}, Xh, Xl, Yh, Yl);
-    hidden(ic<4>{}, std::false_type{}, Yh, Yl, Xh, Xl);
-    hidden(ic<5>{}, std::false_type{}, Xh, Xl, Yh, Yl);
-    hidden(ic<6>{}, std::false_type{}, Yh, Yl, Xh, Xl);
-    hidden(ic<7>{}, std::false_type{}, Xh, Xl, Yh, Yl);
-    hidden(ic<8>{}, std::false_type{}, Yh, Yl, Xh, Xl);
-    hidden(ic<9>{}, std::true_type{}, Xh, Xl, Yh, Yl);
-    // a scaled operand beyond the fp16 range produces infinities, which reach the maxima (fmaxf drops a NaN, not an inf):
-    // report instead of returning garbage
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) bad |= (seg_max[i] & 0x7f800000u) == 0x7f800000u;
-    // lane i publishes segment i, and only if it raises the table (one coherent load + one masked atomic per wave; after the
-    // first few tiles almost no lane has anything to add.  One unconditional atomic per wave and segment -- 90 000 on eleven
-    // addresses -- cost 0.2 ms of the kernel wherever they were issued)
-    unsigned mine = 0;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) mine = lane == i ? seg_max[i] : mine;
-    if (lane < 12 && mine > __hip_atomic_load(a.maxima + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.maxima + lane, mine);
-    if (bad && lane == 0) atomicMax(a.status, 1u);
-}
+// SPARSE: a wave's tile is 16 list SLOTS; lane (g, n) works on sample list[16 * tile + n], gathers its head gradients, rgb
+// and gate words from that sample's row and writes the dZ stash compactly (row = slot).  Slots at or past the count are
+// today's `live == false` lanes.  The grid is that of M samples: a workgroup whose first slot is past the count leaves before
+// it touches the ring, the waves of a partly filled one stay for its barriers.
+#define TGTC_DGRAD_SPARSE 0
+#include "train_dgrad_kernel.inc"
+#undef TGTC_DGRAD_SPARSE
+#define TGTC_DGRAD_SPARSE 1
+#include "train_dgrad_kernel.inc"
+#undef TGTC_DGRAD_SPARSE
 
 }  // namespace train
 }  // namespace tgtc
@@ -638,8 +502,15 @@ __device__ __forceinline__ half8 tr_lo(const TrQuad& r) { return __builtin_bit_c
 // N rows of dW (a dZ slice N wide), K0 + K1 input columns (two H segments), all compile-time: every staging load is
 // unconditional and issued back to back (a load behind a lane-dependent branch made hipcc wait for the previous one first:
 // three memory round trips per step), out-of-range threads re-read a valid unit and skip the LDS store.
-template <int N, int K0, int K1>
-__device__ __forceinline__ void wgrad_body(const WgradArgs& a, const WgradJob& J, int job, long long step0, long long step1, char* smem) {
+//
+// SPARSE (tgtc_trainer_set_sparse): a step is 32 list SLOTS.  The dZ operand is read at slot rows (the chain wrote it
+// compactly), the H operand at rows list[slot]; `count` is the list's length.  A step's list entries are fetched one step
+// ahead of its rows -- a dependent load inside the step would put a second memory round trip into a loop that is bound by
+// the first.  Slots at or past the count read a valid row of H (the last live one) and contribute a dZ of zero, whatever the
+// workspace holds behind the list and the compact stash.
+template <int N, int K0, int K1, bool SPARSE>
+__device__ __forceinline__ void wgrad_body(const WgradArgs& a, const WgradJob& J, int job, long long step0, long long step1, char* smem,
+                                           const unsigned* list, unsigned count) {
     constexpr int KT = (K0 + K1) / 16, NT = N / 16;
     constexpr int SA = wg_stride(N), SB = wg_stride(K0 + K1);   // halves per image row
     constexpr int A_UPR = N / 4, A_UNITS = 32 * A_UPR, A_PER = (A_UNITS + 511) / 512;      // 16-byte units: per row, per step, per thread
@@ -667,45 +538,77 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const WgradJob& J
     const float* pa[A_PER];
     const half_t *pb0h[B0_PER], *pb0l[B0_PER], *pb1h = nullptr, *pb1l = nullptr;
     int la[A_PER], lb0[B0_PER], lb1 = 0;       // LDS offsets (halves); -1: this thread has no such unit
+    // SPARSE: the slot of the step each unit belongs to; the list entries of the step the next load_step reads (ib*) and of
+    // the one behind it (nb*, in flight).  The B pointers then stay on row 0 of their segment.
+    int qa[A_PER], qb0[B0_PER], qb1 = 0;
+    unsigned ib0[B0_PER], nb0[B0_PER], ib1 = 0, nb1 = 0;
 #pragma unroll
     for (int i = 0; i < A_PER; ++i) {
         const int u = t + 512 * i, ue = u < A_UNITS ? u : u % A_UNITS;
         pa[i] = a.dz + seg_at(J.z_col, J.z_n, a.m_pad, step0 * 32 + ue / A_UPR) + J.n0 + 4 * (ue % A_UPR);
         la[i] = u < A_UNITS ? (u / A_UPR) * SA + 4 * (u % A_UPR) : -1;
+        qa[i] = ue / A_UPR;
     }
 #pragma unroll
     for (int i = 0; i < B0_PER; ++i) {
         const int u = t + 512 * i, ue = u < B0_UNITS ? u : u % B0_UNITS;
-        const size_t off = seg_at(J.k_col[0], K0, a.m_pad, step0 * 32 + ue / B0_UPR) + 8 * (ue % B0_UPR);
+        const size_t off = seg_at(J.k_col[0], K0, a.m_pad, SPARSE ? 0 : step0 * 32 + ue / B0_UPR) + 8 * (ue % B0_UPR);
         pb0h[i] = a.h_hi + off, pb0l[i] = a.h_lo + off;
         lb0[i] = u < B0_UNITS ? (u / B0_UPR) * SB + 8 * (u % B0_UPR) : -1;
+        qb0[i] = ue / B0_UPR, ib0[i] = nb0[i] = 0;
     }
     if constexpr (K1 > 0) {
         const int ue = t % B1_UNITS;
-        const size_t off = seg_at(J.k_col[1], K1, a.m_pad, step0 * 32 + ue / B1_UPR) + 8 * (ue % B1_UPR);
+        const size_t off = seg_at(J.k_col[1], K1, a.m_pad, SPARSE ? 0 : step0 * 32 + ue / B1_UPR) + 8 * (ue % B1_UPR);
         pb1h = a.h_hi + off, pb1l = a.h_lo + off;
         lb1 = t < B1_UNITS ? (t / B1_UPR) * SB + K0 + 8 * (t % B1_UPR) : -1;
+        qb1 = ue / B1_UPR;
     }
+    auto load_index = [&](long long step) {    // SPARSE: list entries of `step` (count >= 1 wherever a step exists)
+        const unsigned s0 = (unsigned)step * 32u, last = count - 1u;
+#pragma unroll
+        for (int i = 0; i < B0_PER; ++i) nb0[i] = list[min(s0 + (unsigned)qb0[i], last)];
+        if constexpr (K1 > 0) nb1 = list[min(s0 + (unsigned)qb1, last)];
+    };
+    auto take_index = [&]() {
+#pragma unroll
+        for (int i = 0; i < B0_PER; ++i) ib0[i] = nb0[i];
+        ib1 = nb1;
+    };
     float4v ra[A_PER];
     u4 rb0h[B0_PER], rb0l[B0_PER], rb1h = u4{0, 0, 0, 0}, rb1l = u4{0, 0, 0, 0};
     auto load_step = [&]() {    // the step the pointers stand on; then move them on
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) ra[i] = *reinterpret_cast<const float4v*>(pa[i]), pa[i] += 32 * (size_t)J.z_n;
+        if constexpr (SPARSE) {
 #pragma unroll
-        for (int i = 0; i < B0_PER; ++i) {
-            rb0h[i] = *reinterpret_cast<const u4*>(pb0h[i]), rb0l[i] = *reinterpret_cast<const u4*>(pb0l[i]);
-            pb0h[i] += 32 * K0, pb0l[i] += 32 * K0;
-        }
-        if constexpr (K1 > 0) {
-            rb1h = *reinterpret_cast<const u4*>(pb1h), rb1l = *reinterpret_cast<const u4*>(pb1l);
-            pb1h += 32 * K1, pb1l += 32 * K1;
+            for (int i = 0; i < B0_PER; ++i) {
+                const size_t at = (size_t)ib0[i] * K0;
+                rb0h[i] = *reinterpret_cast<const u4*>(pb0h[i] + at), rb0l[i] = *reinterpret_cast<const u4*>(pb0l[i] + at);
+            }
+            if constexpr (K1 > 0) {
+                const size_t at = (size_t)ib1 * K1;
+                rb1h = *reinterpret_cast<const u4*>(pb1h + at), rb1l = *reinterpret_cast<const u4*>(pb1l + at);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < B0_PER; ++i) {
+                rb0h[i] = *reinterpret_cast<const u4*>(pb0h[i]), rb0l[i] = *reinterpret_cast<const u4*>(pb0l[i]);
+                pb0h[i] += 32 * K0, pb0l[i] += 32 * K0;
+            }
+            if constexpr (K1 > 0) {
+                rb1h = *reinterpret_cast<const u4*>(pb1h), rb1l = *reinterpret_cast<const u4*>(pb1l);
+                pb1h += 32 * K1, pb1l += 32 * K1;
+            }
         }
     };
-    auto store_step = [&]() {
+    auto store_step = [&](long long step) {
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             if (la[i] >= 0) {
-                const float4v v = ra[i];
+                float4v v = ra[i];
+                if constexpr (SPARSE)
+                    if ((unsigned)step * 32u + (unsigned)qa[i] >= count) v = float4v{0.f, 0.f, 0.f, 0.f};
                 bsum += v;
                 unsigned h01, l01, h23, l23;
                 split_pair_signed(v[0] * sc, v[1] * sc, h01, l01);
@@ -729,12 +632,24 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const WgradJob& J
     const half_t* const a_lo = Alo + (8 * G + q) * SA + 4 * p + 16 * nt;
     const int b_row = (8 * G + q) * SB + 4 * p;
 
+    (void)load_index, (void)take_index;
+    if constexpr (SPARSE) {
+        load_index(step0);
+        take_index();
+        if (step0 + 1 < step1) load_index(step0 + 1);
+    }
     load_step();
     for (long long step = step0; step < step1; ++step) {
         __syncthreads();          // everyone is done reading the previous step's images
-        store_step();
+        store_step(step);
         __syncthreads();
-        if (step + 1 < step1) load_step();      // in flight while this step multiplies
+        if (step + 1 < step1) {
+            if constexpr (SPARSE) {
+                take_index();                                   // fetched while the previous step multiplied
+                if (step + 2 < step1) load_index(step + 2);
+            }
+            load_step();                        // in flight while this step multiplies
+        }
         TrQuad qa, qb[2];
         tr_issue(qa, a_hi, a_lo, 4 * SA);
         tr_issue(qb[0], Bhi + b_row, Blo + b_row, 4 * SB);
@@ -791,12 +706,125 @@ __global__ void __launch_bounds__(512, 2) train_wgrad_kernel(WgradArgs a) {
     const long long step0 = a.steps * chunk / nchunk, step1 = a.steps * (chunk + 1) / nchunk;
     const WgradJob J = kWgradJob[job];
     switch (J.layer) {
-        case 0: wgrad_body<128, 64, 0>(a, J, job, step0, step1, smem); break;
-        case 5: wgrad_body<128, 256, 64>(a, J, job, step0, step1, smem); break;
-        case 8: wgrad_body<16, 256, 0>(a, J, job, step0, step1, smem); break;
-        case 10: wgrad_body<128, 256, 32>(a, J, job, step0, step1, smem); break;
-        case 11: wgrad_body<16, 128, 0>(a, J, job, step0, step1, smem); break;
-        default: wgrad_body<128, 256, 0>(a, J, job, step0, step1, smem); break;
+        case 0: wgrad_body<128, 64, 0, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+        case 5: wgrad_body<128, 256, 64, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+        case 8: wgrad_body<16, 256, 0, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+        case 10: wgrad_body<128, 256, 32, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+        case 11: wgrad_body<16, 128, 0, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+        default: wgrad_body<128, 256, 0, false>(a, J, job, step0, step1, smem, nullptr, 0); break;
+    }
+}
+
+// The sparse instance: the grid and the jobs' chunk counts are those of M samples (the host does not know the count); the
+// steps are ceil(count / 32), read here, and a chunk that gets none of them adds nothing.
+__global__ void __launch_bounds__(512, 2) train_wgrad_sparse_kernel(WgradArgs a, LiveList sp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int job = 0;
+#pragma unroll
+    for (int j = 1; j < kWgradJobs; ++j)
+        if ((int)blockIdx.x >= a.chunk0[j]) job = j;
+    const int nchunk = a.chunk0[job + 1] - a.chunk0[job], chunk = (int)blockIdx.x - a.chunk0[job];
+    const unsigned count = __builtin_amdgcn_readfirstlane(*sp.count);
+    const long long steps = (long long)((count + 31u) / 32u);
+    const long long step0 = steps * chunk / nchunk, step1 = steps * (chunk + 1) / nchunk;
+    if (step0 >= step1) return;
+    const WgradJob J = kWgradJob[job];
+    switch (J.layer) {
+        case 0: wgrad_body<128, 64, 0, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+        case 5: wgrad_body<128, 256, 64, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+        case 8: wgrad_body<16, 256, 0, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+        case 10: wgrad_body<128, 256, 32, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+        case 11: wgrad_body<16, 128, 0, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+        default: wgrad_body<128, 256, 0, true>(a, J, job, step0, step1, smem, sp.list, count); break;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ live list
+// The ordered compaction of the render's live lists (mlp_style_sparse.hip: count, sums in front, scatter) with the
+// trainer's predicate: sample m is live iff not all of d_sigma[m], d_rgb[m, 0..2] compare == 0.0f -- -0.0 is dead, NaN and
+// inf are live (the overflow guard still sees them).  The M samples are cut into kLiveParts contiguous ranges of `span`
+// (a multiple of the block); pass 1 counts each range, pass 2 sums the counts in front of its range and writes the range's
+// live indices behind them in lane order: ascending, no atomics on the list.  The last block of pass 2 writes the count and
+// adds (count, M) to the trainer's running sums (tgtc_trainer_live_counts).
+constexpr int kLiveParts = 1024;
+constexpr int kLiveBlock = 256;
+
+__device__ __forceinline__ bool grad_live(const float* __restrict__ d_rgb, const float* __restrict__ d_sigma, unsigned m) {
+    return !(d_sigma[m] == 0.0f && d_rgb[3 * (size_t)m] == 0.0f && d_rgb[3 * (size_t)m + 1] == 0.0f && d_rgb[3 * (size_t)m + 2] == 0.0f);
+}
+
+__global__ void __launch_bounds__(kLiveBlock) live_count_kernel(const float* __restrict__ d_rgb, const float* __restrict__ d_sigma,
+                                                                unsigned M, unsigned span, unsigned* __restrict__ counts) {
+    __shared__ unsigned wave_n[kLiveBlock / 64];
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * span;
+    const unsigned lo = b0 < M ? (unsigned)b0 : M;
+    const unsigned hi = b0 + span < M ? (unsigned)(b0 + span) : M;
+    unsigned cnt = 0;
+    for (unsigned s = lo + threadIdx.x; s < hi; s += kLiveBlock) cnt += grad_live(d_rgb, d_sigma, s) ? 1u : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned tot = 0;
+#pragma unroll
+        for (int i = 0; i < kLiveBlock / 64; ++i) tot += wave_n[i];
+        counts[blockIdx.x] = tot;
+    }
+}
+
+__global__ void __launch_bounds__(kLiveBlock) live_write_kernel(const float* __restrict__ d_rgb, const float* __restrict__ d_sigma,
+                                                                unsigned M, unsigned span, const unsigned* __restrict__ counts,
+                                                                unsigned* __restrict__ list, unsigned* __restrict__ n_live,
+                                                                unsigned long long* __restrict__ sums) {
+    __shared__ unsigned red[kLiveBlock / 64];
+    __shared__ unsigned wave_n[2][kLiveBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned before = 0, all = 0;      // live samples of the ranges in front of this one; of all ranges
+    for (unsigned p = threadIdx.x; p < kLiveParts; p += kLiveBlock) {
+        const unsigned c = counts[p];
+        all += c;
+        if (p < blockIdx.x) before += c;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d), all += __shfl_xor(all, d);
+    if (lane == 0) red[wave] = before;
+    __syncthreads();
+    unsigned base = 0;
+#pragma unroll
+    for (int i = 0; i < kLiveBlock / 64; ++i) base += red[i];
+    if (blockIdx.x == kLiveParts - 1) {
+        __syncthreads();
+        if (lane == 0) red[wave] = all;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned tot = 0;
+#pragma unroll
+            for (int i = 0; i < kLiveBlock / 64; ++i) tot += red[i];
+            *n_live = tot;
+            atomicAdd(sums, (unsigned long long)tot);
+            atomicAdd(sums + 1, (unsigned long long)M);
+        }
+    }
+    const unsigned long long b0 = (unsigned long long)blockIdx.x * span;
+    const unsigned lo = b0 < M ? (unsigned)b0 : M;
+    const unsigned hi = b0 + span < M ? (unsigned)(b0 + span) : M;
+    int it = 0;
+    for (unsigned s0 = lo; s0 < hi; s0 += kLiveBlock, ++it) {      // whole steps for every thread: the barrier is reached by all
+        const unsigned s = s0 + threadIdx.x;
+        const bool keep = s < hi && grad_live(d_rgb, d_sigma, s);
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_n[it & 1][wave] = (unsigned)__popcll(m);
+        __syncthreads();   // the buffer written two steps ago is free: every wave has passed the barrier in between
+        unsigned at = base, step = 0;
+#pragma unroll
+        for (int i = 0; i < kLiveBlock / 64; ++i) {
+            const unsigned c = wave_n[it & 1][i];
+            if (i < wave) at += c;
+            step += c;
+        }
+        if (keep) list[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = s;   // at + rank < count <= M
+        base += step;
     }
 }
 
@@ -870,7 +898,7 @@ extern "C" int tgtc_trainer_create(tgtc_trainer** out) {
     tr->bwd_map_off = take(bwd.size() * sizeof(PackSrc));
     tr->fwd_bias_map_off = take(bias.size() * sizeof(PackSrc));
     tr->unperm_off = take(unperm.size() * sizeof(short));
-    tr->maxima_off = take(64);                                                         // 12 segment maxima + status word
+    tr->maxima_off = take(128);      // 12 segment maxima, status word, overflow counter; at +64 the live / total sums (2 x 64 bits)
     tr->fwd_stream_off = take(kNerfBiasBytes + tr->fwd_stream_bytes + kRingBytes);     // [bias table][stream][slack for the look-ahead]
     tr->bwd_stream_off = take(kNerfBiasBytes + tr->bwd_stream_bytes + kRingBytes);     // [zeros][stream][slack]
     hipError_t e = hipMalloc((void**)&tr->dev, off);
@@ -926,6 +954,15 @@ extern "C" int tgtc_trainer_destroy(tgtc_trainer* tr) {
 }
 
 extern "C" size_t tgtc_trainer_workspace_bytes(int64_t M) { return M > 0 ? ws_layout(M).total : 0; }
+extern "C" size_t tgtc_trainer_workspace_bytes_sparse(int64_t M) { return M > 0 ? ws_layout(M).total_sparse : 0; }
+static_assert(kLivePartsBytes == kLiveParts * sizeof(unsigned), "partial counts of the compaction");
+
+extern "C" int tgtc_trainer_set_sparse(tgtc_trainer* tr, int mode) {
+    TGTC_REQUIRE(tr, "trainer_set_sparse: null argument");
+    TGTC_REQUIRE(mode == TGTC_TRAIN_DENSE || mode == TGTC_TRAIN_SPARSE, "trainer_set_sparse: mode %d (TGTC_TRAIN_DENSE 0, TGTC_TRAIN_SPARSE 1)", mode);
+    tr->sparse = mode;
+    return TGTC_OK;
+}
 
 static int check_params(const float* const* params, const char* who) {
     TGTC_REQUIRE(params, "%s: null parameter table", who);
@@ -967,6 +1004,11 @@ extern "C" int tgtc_trainer_backward(tgtc_trainer* tr, const float* const* param
     if (int rc = check_params(params, "trainer_backward")) return rc;
     for (int i = 0; i < 24; ++i) TGTC_REQUIRE(grads[i], "trainer_backward: gradient %d is null", i);
     const WsLayout w = ws_layout(M);
+    // (the mode is the caller's: a workspace of the dense size never turns a sparse backward into a dense one)
+    const bool sparse = tr->sparse == TGTC_TRAIN_SPARSE;
+    if (sparse)
+        TGTC_REQUIRE(workspace_bytes >= w.total_sparse, "trainer_backward: sparse mode with a workspace of %zu bytes, need %zu (tgtc_trainer_workspace_bytes_sparse)",
+                     workspace_bytes, w.total_sparse);
     TGTC_REQUIRE(workspace_bytes >= w.total, "trainer_backward: workspace of %zu bytes, need %zu", workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     ParamPtrs pp;
@@ -998,7 +1040,23 @@ extern "C" int tgtc_trainer_backward(tgtc_trainer* tr, const float* const* param
     b.zero_bias = bs, b.stream = bs + kNerfBiasBytes, b.M = M, b.rgb = rgb, b.d_rgb = d_rgb, b.d_sigma = d_sigma;
     b.gates = reinterpret_cast<const unsigned long long*>(ws + w.gates), b.n_tiles = w.n_tiles;
     b.dz = reinterpret_cast<float*>(ws + w.dz), b.maxima = maxima, b.status = maxima + 12;
-    train_dgrad_kernel<<<(unsigned)(w.m_pad / kTileSamples), CfgT::NWAVES * 64, 0, st>>>(b);
+    LiveList sp{};
+    if (sparse) {
+        unsigned* const list = reinterpret_cast<unsigned*>(ws + w.list);
+        unsigned* const count = reinterpret_cast<unsigned*>(ws + w.count);
+        unsigned* const parts = reinterpret_cast<unsigned*>(ws + w.parts);
+        const int64_t per = (M + kLiveParts - 1) / kLiveParts;      // span: a multiple of the block with kLiveParts * span >= M
+        const unsigned span = (unsigned)((per + kLiveBlock - 1) / kLiveBlock * kLiveBlock);
+        live_count_kernel<<<kLiveParts, kLiveBlock, 0, st>>>(d_rgb, d_sigma, (unsigned)M, span, parts);
+        TGTC_LAUNCH_CHECK();
+        live_write_kernel<<<kLiveParts, kLiveBlock, 0, st>>>(d_rgb, d_sigma, (unsigned)M, span, parts, list, count,
+                                                             reinterpret_cast<unsigned long long*>(tr->dev + tr->maxima_off + 64));
+        TGTC_LAUNCH_CHECK();
+        sp.list = list, sp.count = count;
+        train_dgrad_sparse_kernel<<<(unsigned)(w.m_pad / kTileSamples), CfgT::NWAVES * 64, 0, st>>>(b, sp);
+    } else {
+        train_dgrad_kernel<<<(unsigned)(w.m_pad / kTileSamples), CfgT::NWAVES * 64, 0, st>>>(b);
+    }
     TGTC_LAUNCH_CHECK();
 
     WgradArgs g{};
@@ -1011,8 +1069,13 @@ extern "C" int tgtc_trainer_backward(tgtc_trainer* tr, const float* const* param
     // (In proportion to the multiply count the two one-tile jobs ran all 4 096 steps in ONE workgroup: 4 ms.)
     g.chunk0[0] = 0;
     for (int j = 0; j < kWgradJobs; ++j) g.chunk0[j + 1] = g.chunk0[j] + (int)std::min<long long>(12, g.steps);
-    TGTC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(train_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kWgLdsBytes));
-    train_wgrad_kernel<<<(unsigned)g.chunk0[kWgradJobs], 512, kWgLdsBytes, st>>>(g);
+    if (sparse) {      // the same grid: the count is on the device, a chunk without steps leaves at once
+        TGTC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(train_wgrad_sparse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kWgLdsBytes));
+        train_wgrad_sparse_kernel<<<(unsigned)g.chunk0[kWgradJobs], 512, kWgLdsBytes, st>>>(g, sp);
+    } else {
+        TGTC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(train_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kWgLdsBytes));
+        train_wgrad_kernel<<<(unsigned)g.chunk0[kWgradJobs], 512, kWgLdsBytes, st>>>(g);
+    }
     TGTC_LAUNCH_CHECK();
     GuardArgs ga{};
     for (int l = 0; l < 12; ++l) {
@@ -1032,6 +1095,15 @@ extern "C" int tgtc_trainer_overflows(tgtc_trainer* tr, void* stream, unsigned* 
     TGTC_REQUIRE(tr && count, "trainer_overflows: null argument");
     TGTC_HIP_CHECK(hipMemcpyAsync(count, tr->dev + tr->maxima_off + 52, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
     TGTC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_trainer_live_counts(tgtc_trainer* tr, void* stream, unsigned long long* live, unsigned long long* total) {
+    TGTC_REQUIRE(tr && live && total, "trainer_live_counts: null argument");
+    unsigned long long sums[2] = {0, 0};
+    TGTC_HIP_CHECK(hipMemcpyAsync(sums, tr->dev + tr->maxima_off + 64, sizeof(sums), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    TGTC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    *live = sums[0], *total = sums[1];
     return TGTC_OK;
 }
 

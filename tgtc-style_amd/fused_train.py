@@ -24,8 +24,12 @@ SIGNATURES = {
     "tgtc_trainer_backward": [c_void_p, _PTRS, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, _PTRS, c_void_p],
     "tgtc_trainer_status": [c_void_p, c_void_p],
     "tgtc_trainer_overflows": [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint)],
+    "tgtc_trainer_set_sparse": [c_void_p, c_int],
+    "tgtc_trainer_workspace_bytes_sparse": [c_int64],
+    "tgtc_trainer_live_counts": [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)],
 }
-hip.register(SIGNATURES, {"tgtc_trainer_workspace_bytes": c_size_t})
+hip.register(SIGNATURES, {"tgtc_trainer_workspace_bytes": c_size_t, "tgtc_trainer_workspace_bytes_sparse": c_size_t})
+TRAIN_DENSE, TRAIN_SPARSE = 0, 1     # include/tgtc_train.h
 
 
 def mlp_parameters(net):
@@ -53,14 +57,21 @@ class NerfTrainer:
     to ONE forward / backward pair: `lease` hands one out per forward, the autograd node keeps it until its backward has
     run and `release` returns it to the pool.  Two forwards before one backward -- the reference's batchify
     (utils.py:435-456), gradient accumulation -- therefore hold two workspaces; `drop_workspaces` frees the pool
-    (StyleNerf.trainable(False))."""
+    (StyleNerf.trainable(False)).
 
-    def __init__(self):
+    sparse=True: the sparse backward (include/tgtc_train.h) -- input-gradient chain and weight gradients over the samples
+    whose upstream gradient is not exactly zero; `lease` then hands out the larger workspace that mode needs.  The mode is
+    fixed at construction and never chosen by the library."""
+
+    def __init__(self, sparse=False):
         self.lib = hip.load()
         h = c_void_p()
         hip.check(self.lib.tgtc_trainer_create(ctypes.byref(h)))
         self.handle = h
         self._pool = []
+        self.sparse = bool(sparse)
+        if self.sparse:
+            hip.check(self.lib.tgtc_trainer_set_sparse(self.handle, TRAIN_SPARSE))
 
     def __del__(self):
         try:
@@ -71,7 +82,7 @@ class NerfTrainer:
 
     def lease(self, M, device):
         """a workspace for one forward / backward pair of M samples"""
-        need = int(self.lib.tgtc_trainer_workspace_bytes(M))
+        need = int(self.lib.tgtc_trainer_workspace_bytes_sparse(M) if self.sparse else self.lib.tgtc_trainer_workspace_bytes(M))
         if need > MAX_WORKSPACE_BYTES:
             raise ValueError("fused training workspace for %d samples = %.1f GiB (about 20 KB per sample): chunk the batch "
                              "(utils.batchify) or train on the per-layer path (.trainable(fused=False))" % (M, need / 2.0 ** 30))
@@ -120,6 +131,13 @@ class NerfTrainer:
         n = ctypes.c_uint(0)
         hip.check(self.lib.tgtc_trainer_overflows(self.handle, hip.stream(), ctypes.byref(n)))
         return int(n.value)
+
+    def live_counts(self):
+        """(live, total): samples whose upstream gradient was not all zero / all samples, summed over the sparse backwards
+        since creation -- dense backwards add nothing (synchronises; read it where `overflows` is read)"""
+        live, total = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        hip.check(self.lib.tgtc_trainer_live_counts(self.handle, hip.stream(), ctypes.byref(live), ctypes.byref(total)))
+        return int(live.value), int(total.value)
 
     def apply(self, net, pts, dirs):
         """pts, dirs: [..., 3] (any float dtype) -> rgb [..., 3], sigma [...]"""

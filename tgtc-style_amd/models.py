@@ -165,17 +165,24 @@ class StyleNerf(nn.Module):
         self.enable_style = enable_style
         self.fused_training, self._trainer = False, None
 
-    def trainable(self, on=True, fused=True):
+    def trainable(self, on=True, fused=True, sparse=False):
         """Training side: whenever gradients are enabled the forward becomes differentiable w.r.t. the 24 parameters (the
         render paths stay on the fused forward-only kernels).  fused=True (default): the fused training path
         (fused_train.py / csrc/mlp_train.hip: forward with activation stash, input-gradient chain and weight gradients as
         three launches; returns the dict entries a training body reads -- rgb and sigma).  fused=False: the same arithmetic
-        layer by layer on differentiable HIP dense layers (autograd_ops.py), with every entry of the render-path dict."""
+        layer by layer on differentiable HIP dense layers (autograd_ops.py), with every entry of the render-path dict.
+        sparse=True (fused only; never chosen for the caller): the backward runs over the samples whose upstream gradient
+        is not exactly zero (include/tgtc_train.h, "Sparse backward"); `training_live_counts` tells how many those were."""
+        if sparse and not fused:
+            raise ValueError("StyleNerf.trainable: sparse=True is a mode of the fused training kernels (fused=True); the "
+                             "per-layer path has no sparse backward")
         self.net.differentiable = bool(on)
         self.fused_training = bool(on and fused)
+        if self.fused_training and self._trainer is not None and self._trainer.sparse != bool(sparse):
+            self._trainer = None                    # the mode belongs to the trainer: another mode, another trainer
         if self.fused_training and self._trainer is None:
             from . import fused_train
-            self._trainer = fused_train.NerfTrainer()
+            self._trainer = fused_train.NerfTrainer(sparse=sparse)
         if not on and self._trainer is not None:
             self._trainer.drop_workspaces()         # ~20 KB per sample of the largest batch seen (fused_train.NerfTrainer)
         return self
@@ -185,6 +192,11 @@ class StyleNerf(nn.Module):
         input gradients left the fp16 range; include/tgtc_train.h).  Synchronises: read it where the reference prints its
         losses (every i_print iterations, train_tgtcs.py:257-266)."""
         return 0 if self._trainer is None else self._trainer.overflows()
+
+    def training_live_counts(self):
+        """(live, total) samples of the sparse backwards of the fused training path since the trainer was made -- (0, 0)
+        without one or in dense mode.  Synchronises, like `training_overflows`."""
+        return (0, 0) if self._trainer is None else self._trainer.live_counts()
 
     def set_enable_style(self, enable_style=False):
         self.enable_style = enable_style

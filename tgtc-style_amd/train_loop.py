@@ -226,7 +226,8 @@ def origin_train(args, model, model_fine, data, sv_path, global_step, optimizer_
     if log is None:
         last_log = log = []
     fused = not getattr(args, "train_unfused", False)
-    model.trainable(fused=fused), model_fine.trainable(fused=fused)
+    sparse = bool(getattr(args, "train_sparse", False))          # --train_sparse: only ever the caller's choice
+    model.trainable(fused=fused, sparse=sparse), model_fine.trainable(fused=fused, sparse=sparse)
     optimizer = make_optimizer(args, model, model_fine)
     if optimizer_state:
         optimizer.load_state_dict(optimizer_state)
@@ -238,6 +239,7 @@ def origin_train(args, model, model_fine, data, sv_path, global_step, optimizer_
     backwards_per_step = (2 if n_fine > 0 else 1) if fused else 0
     overflows = lambda: model.training_overflows() + model_fine.training_overflows()
     count_before = overflows()
+    live_before = (model.training_live_counts(), model_fine.training_live_counts()) if sparse else None
     acc = torch.zeros((), device=data.device)          # sum of the losses since the previous line, on the device
     window, t0 = 0, time.perf_counter()
     while True:
@@ -265,6 +267,13 @@ def origin_train(args, model, model_fine, data, sv_path, global_step, optimizer_
             else:
                 line += " RGB Loss: %s" % vals[1]
             line += " Mean loss of %d step(s): %s %.1f steps/s" % (window, entry['mean_loss'], entry['steps_per_s'])
+            if sparse:
+                # the window's live share of each network's sparse backwards, read where the overflow counters are read
+                live_now = (model.training_live_counts(), model_fine.training_live_counts())
+                shares = [(n[0] - b[0]) / (n[1] - b[1]) if n[1] > b[1] else 0. for b, n in zip(live_before, live_now)]
+                entry.update(live_coarse=shares[0], live_fine=shares[1])
+                line += " Live: %.3f coarse %.3f fine" % (shares[0], shares[1])
+                live_before = live_now
             message, abort = overflow_policy(count_before, count_now, backwards_per_step * window)
             if message and not abort:
                 line += " -- " + message

@@ -454,6 +454,19 @@ def main(argv=None):
             raise SystemExit("train_tgtcs: --two_phase needs --render_valid or --render_train and nothing else (it is the fine "
                              "pass of the plain render on the chain%s)"
                              % ("; it does not go with --" + " / --".join(others) if others else ""))
+    if args.train_sparse:
+        renders = [f for f in ("render_valid", "render_train", "render_valid_style", "render_train_style") if getattr(args, f)]
+        if args.train_unfused:
+            raise SystemExit("train_tgtcs: --train_sparse is a mode of the fused training kernels; it does not go with "
+                             "--train_unfused (the per-layer path has no sparse backward)")
+        if args.style_train:
+            raise SystemExit("train_tgtcs: --train_sparse goes with --origin_train; it does not go with --style_train (the "
+                             "NeRF pair is frozen there: no NeRF backward runs)")
+        if renders:
+            raise SystemExit("train_tgtcs: --train_sparse goes with --origin_train; it does not go with --%s (a render "
+                             "runs no backward)" % " / --".join(renders))
+        if not args.origin_train:
+            raise SystemExit("train_tgtcs: --train_sparse needs --origin_train (it is the backward of that stage)")
     if args.origin_train and args.style_train:
         raise SystemExit("train_tgtcs: --origin_train and --style_train are two stages: one call each, in that order")
     for stage in ("origin_train", "style_train"):
