@@ -29,7 +29,10 @@ size_t tgtc_trainer_workspace_bytes(int64_t M);
 int tgtc_trainer_forward(tgtc_trainer* trainer, const float* const* params, const double* pts, const double* dirs, int64_t M,
                          void* workspace, size_t workspace_bytes, float* rgb, float* sigma, void* stream);
 /* backward of the same call (same M, same workspace, untouched in between): rgb = the forward's output, d_rgb [M,3] and
- * d_sigma [M] = dL/d outputs; grads[i] (shapes of params[i]) are OVERWRITTEN with dL/d params[i]. */
+ * d_sigma [M] = dL/d outputs; grads[i] (shapes of params[i]) are OVERWRITTEN with dL/d params[i].
+ * grads[17], d sigma_layer.bias, is ONE number -- the sum of d_sigma -- and is taken in float64 in a fixed order and rounded
+ * once (one small launch after the weight gradients, dense and sparse mode alike): the same bits at every call, also where
+ * the summands cancel.  Every other gradient is accumulated in float32 by atomics, in whatever order they land. */
 int tgtc_trainer_backward(tgtc_trainer* trainer, const float* const* params, const float* rgb, const float* d_rgb,
                           const float* d_sigma, int64_t M, void* workspace, size_t workspace_bytes, float* const* grads,
                           void* stream);
@@ -103,6 +106,56 @@ int tgtc_style_train_batch(int H, int W, double fx, double fy, double cx, double
                            int coh_style, int coh_frame, int64_t coh_start, int pixel_alignment, int ndc, double ndc_near,
                            double* rays_o, double* rays_d, float* rgb_gt, float* rgb_origin, int64_t* style_id,
                            int64_t* frame_id, void* stream);
+
+/* Style trainer (csrc/style2d.hip): forward and backward of BOTH style MLPs of `Style_train` -- StyleMLP_before_concat
+ * (models.py:120-147, 5 linears) feeding StyleMLP_Wild_multilayers (models.py:149-180, 7 hidden linears and the 3-wide
+ * sigmoid head) -- in two calls, in place of one GEMM call per layer and pass from a binding (tgtc_s2d_linear_pre /
+ * tgtc_s2d_linear_backward).  It is the same per-layer arithmetic on the same GEMM kernel, chained inside the library; no
+ * layer input is ever concatenated: the GEMM's row loader reads the segments in place.
+ *   x           DEVICE float [M,63]   the encoded sample points (ret['pts']), M = R * n, sample m belongs to ray m / n
+ *   base_remap  DEVICE float [M,256]  the NeRF trunk's remap features
+ *   lat_c       DEVICE float [R,32]   one latent row per ray, read by every layer of the concat MLP
+ *   lat_s       DEVICE float [R,32]   the style MLP's latent row (the reference hands it mean(z) in all 32 columns)
+ *   rgb         DEVICE float [M,3]
+ * Layer inputs, in the column order of the weights: concat 0 [x | lat_c], 1-3 [h | lat_c], 4 [h | lat_c | x]; style 0
+ * [base_remap | concat output | x | lat_s], 1-3, 5, 6 and the head [h | lat_s], 4 [h | lat_s | x].
+ * `params` / `grads`: HOST arrays of 26 DEVICE pointers -- the concat MLP's layers[0..4], then the style MLP's layers[0..7],
+ * weight ([out, in] row-major fp32) then bias for each.  The weights are read on the device at every call.  Every layer's
+ * output equals, bit for bit, tgtc_s2d_linear_pre on the concatenated input (halves from tgtc_s2d_split where in % 4 == 0).
+ * `precision`: TGTC_PREC_FP16X3 or TGTC_PREC_FP16, of the forward and of the backward that follows it.
+ *
+ * Backward (same R, n and workspace as the forward, workspace untouched in between; x, base_remap, lat_c and lat_s of the
+ * forward are read again and must still hold the same values): d_rgb [M,3] = dL/d rgb; grads[i] (shape of params[i]) is
+ * OVERWRITTEN with dL/d params[i]; d_lat_c / d_lat_s float [R,32], each may be NULL, are overwritten with dL/d lat_c /
+ * dL/d lat_s -- per layer the gated gradient rows of a ray are summed first and multiplied by the latent columns of the
+ * weight once per ray.  x and base_remap receive no gradient.  Gradient scaling is that of tgtc_s2d_linear_backward.  A
+ * backward consumes the forward's record: a second backward on one forward is TGTC_ERR_ARG.
+ *
+ * Workspace: about 19 KB per sample -- 12 fp32 activation planes of 256 (12 KB) and rgb, kept from forward to backward, and
+ * the backward's per-layer scratch, reused layer after layer: two gradient planes of 256, the row-scaled gradient, the
+ * transposed fp16 hi/lo gradient (256 columns) and input (607 columns) -- plus at most 12 MB that do not grow with M.  It
+ * belongs to ONE forward / backward pair, like tgtc_trainer's: Style_train's coarse and fine passes hold two.
+ * R == 0 is TGTC_OK (backward then zero-fills grads).  TGTC_ERR_ARG with nothing launched: a NULL trainer, params, grads (or
+ * entry of them), x, base_remap, lat_c, lat_s, rgb, d_rgb or workspace; R < 0, n <= 0, R * n > 2 097 120 (65 535 x 32: the
+ * sample dimension of the weight-gradient transposes is a grid dimension; larger batches go in chunks, their gradients
+ * added); a workspace below tgtc_style_trainer_workspace_bytes(R, n) (0 for a shape that is refused); any other precision;
+ * a backward without its forward.
+ * The record of a forward (a few words on the host, keyed by the workspace's address) is dropped by its backward, replaced
+ * by the next forward into the same workspace, and freed with the trainer -- by nothing else.  A forward whose backward
+ * never runs leaves it behind; if its workspace is then freed and another allocation lands on the same address, a
+ * backward of the same (R, n) into that memory WITHOUT a forward is not refused, and reads whatever the memory holds.
+ * Callers that drop forwards (evaluation, an exception between the two calls) keep their workspaces, as a pool does, or
+ * destroy the trainer. */
+typedef struct tgtc_style_trainer tgtc_style_trainer; /* opaque: which forward each workspace holds */
+int tgtc_style_trainer_create(tgtc_style_trainer** out);
+int tgtc_style_trainer_destroy(tgtc_style_trainer* trainer);
+size_t tgtc_style_trainer_workspace_bytes(int64_t R, int n);
+int tgtc_style_trainer_forward(tgtc_style_trainer* trainer, const float* const* params, const float* x, const float* base_remap,
+                               const float* lat_c, const float* lat_s, int64_t R, int n, int precision, void* workspace,
+                               size_t workspace_bytes, float* rgb, void* stream);
+int tgtc_style_trainer_backward(tgtc_style_trainer* trainer, const float* const* params, const float* d_rgb, int64_t R, int n,
+                                void* workspace, size_t workspace_bytes, float* const* grads, float* d_lat_c, float* d_lat_s,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,7 @@ EXTRA = {
     "style_train": (None, False),      # run the reference's Style_train loop: style MLPs and latent table (HELP below)
     "coh_until": (int, 122000),        # --style_train: last step with the coherence term in the style optimiser's loss
     "latent_lrate": (float, 1e-3),     # --style_train: learning rate of the latent table's own Adam
+    "style_chain": (None, False),      # --style_train: both style MLPs through the library's style trainer (HELP below)
 }
 
 
@@ -92,6 +93,11 @@ HELP = {
     "coh_until": "with --style_train: the coherence term is part of the style optimiser's loss while step <= this "
                  "(default 122000, the reference's literal)",
     "latent_lrate": "with --style_train: learning rate of the latent table's own Adam (default 1e-3, the reference's literal)",
+    "style_chain": "with --style_train: run the forward and the backward of the two style MLPs as two calls of the library's "
+                   "style trainer (tgtc_style_trainer_forward / _backward: the per-layer GEMMs chained inside the library, "
+                   "layer inputs read in place, the latent gradient summed per ray) in place of 26 differentiable layer "
+                   "calls per pass.  Same forward bits, gradients equal up to fp32 / fp16x3 rounding.  Never switched on by "
+                   "itself.  Refused together with --origin_train and any --render_* flag",
     "synthetic_styles": "styles of the synthetic scene's latent table (default 1)",
     "share_geometry": "with --render_valid_style: render all styles of a frame in one multi-latent call that shares the "
                       "coarse pass, the fine depths and the fine NeRF trunk.  Style 0 is rendered with the jitter it has "

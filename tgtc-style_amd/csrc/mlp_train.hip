@@ -870,6 +870,7 @@ void build_unperm(std::vector<short>& out) {
 
 }  // namespace
 
+constexpr int kSigmaBiasBlocks = 64;      // blocks of sigma_bias_kernel (below): one wave adds their partials
 extern "C" int tgtc_trainer_create(tgtc_trainer** out) {
     TGTC_REQUIRE(out, "trainer_create: null argument");
     std::vector<PackSrc> fwd, bwd, bias;
@@ -898,7 +899,7 @@ extern "C" int tgtc_trainer_create(tgtc_trainer** out) {
     tr->bwd_map_off = take(bwd.size() * sizeof(PackSrc));
     tr->fwd_bias_map_off = take(bias.size() * sizeof(PackSrc));
     tr->unperm_off = take(unperm.size() * sizeof(short));
-    tr->maxima_off = take(128);      // 12 segment maxima, status word, overflow counter; at +64 the live / total sums (2 x 64 bits)
+    tr->maxima_off = take(128 + kSigmaBiasBlocks * sizeof(double));      // 12 segment maxima, status word, overflow counter; at +64 the live / total sums (2 x 64 bits); at +96 sigma_bias_kernel's arrival counter, at +128 its block partials
     tr->fwd_stream_off = take(kNerfBiasBytes + tr->fwd_stream_bytes + kRingBytes);     // [bias table][stream][slack for the look-ahead]
     tr->bwd_stream_off = take(kNerfBiasBytes + tr->bwd_stream_bytes + kRingBytes);     // [zeros][stream][slack]
     hipError_t e = hipMalloc((void**)&tr->dev, off);
@@ -943,6 +944,37 @@ __global__ void __launch_bounds__(256) overflow_guard_kernel(const unsigned* sta
     for (int i = 0; i < 24; ++i)
         for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < a.n[i]; k += gridDim.x * blockDim.x) a.g[i][k] = 0.0f;
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(count, 1u);
+}
+
+// d sigma_layer.bias is ONE number, the sum of d_sigma over the samples (the sigma head has no activation of its own), and
+// under any rule relative to the tensor's maximum it must be right relative to ITSELF.  Where the summands cancel (a mask
+// that leaves -9.4e-8 of sum |d_sigma| = 3.9e-4) the float32 column sum of the weight-gradient kernel lands anywhere within
+// 1e-4 of it, by the order in which its atomics arrive.  This sum is taken again in float64 in a FIXED order -- block b sums
+// its samples (strided, then a shuffle tree) into part[b]; the last block to arrive adds the partials in a shuffle tree over
+// b -- and OVERWRITES the kernel's value: the same bits whatever the order of arrival.  Dead samples of the sparse mode carry
+// d_sigma == +-0 and add nothing; a non-finite d_sigma reaches the guard's scan.  arrived: zeroed by the caller.
+__global__ void __launch_bounds__(256) sigma_bias_kernel(const float* __restrict__ d_sigma, long long M, unsigned* __restrict__ arrived,
+                                                         double* __restrict__ part, float* __restrict__ db) {
+    __shared__ double red[4];
+    __shared__ bool last;
+    double s = 0.0;
+    for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < M; m += (long long)gridDim.x * 256) s += (double)d_sigma[m];
+#pragma unroll
+    for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(part + blockIdx.x, (red[0] + red[1]) + (red[2] + red[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = atomicAdd(arrived, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || threadIdx.x >= 64) return;      // (block-uniform, then wave-uniform)
+    __threadfence();
+    double t = threadIdx.x < gridDim.x ? __hip_atomic_load(part + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+#pragma unroll
+    for (int off = 32; off; off >>= 1) t += __shfl_xor(t, off);
+    if (threadIdx.x == 0) db[0] = (float)t;
 }
 
 extern "C" int tgtc_trainer_destroy(tgtc_trainer* tr) {
@@ -1077,6 +1109,15 @@ extern "C" int tgtc_trainer_backward(tgtc_trainer* tr, const float* const* param
         train_wgrad_kernel<<<(unsigned)g.chunk0[kWgradJobs], 512, kWgLdsBytes, st>>>(g);
     }
     TGTC_LAUNCH_CHECK();
+    {   // d sigma_layer.bias again, in float64, over the kernel's float32 column sum (sigma_bias_kernel)
+#ifndef TGTC_ABL_NOSIGMABIAS   // (development builds leave it out: tools/time_sigma_bias.py times the backward with and without)
+        unsigned* const arrived = reinterpret_cast<unsigned*>(tr->dev + tr->maxima_off + 96);
+        TGTC_HIP_CHECK(hipMemsetAsync(arrived, 0, sizeof(unsigned), st));
+        sigma_bias_kernel<<<(unsigned)std::min<long long>(kSigmaBiasBlocks, (M + 255) / 256), 256, 0, st>>>(
+            d_sigma, M, arrived, reinterpret_cast<double*>(tr->dev + tr->maxima_off + 128), grads[2 * 8 + 1]);
+        TGTC_LAUNCH_CHECK();
+#endif
+    }
     GuardArgs ga{};
     for (int l = 0; l < 12; ++l) {
         ga.g[2 * l] = grads[2 * l], ga.n[2 * l] = (unsigned)(shape[l][0] * shape[l][1]);

@@ -12,10 +12,12 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/tgtc_style2d.h"
+#include "../../include/tgtc_train.h"
 #include "common.h"
 #include "mlp_core.h"
 
@@ -45,6 +47,48 @@ struct DenseRows {  // A(m,k) = p[m*ld + k]
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = (c.row && k + j < K) ? c.row[k + j] : 0.0f;
+        }
+    }
+};
+
+// A(m, k) = the k-th column of a concatenation of up to four segments that is never materialised (the layer inputs of the
+// style trainer, include/tgtc_train.h).  A segment is a per-sample plane (row m) or a per-ray one (row m / n, n samples per
+// ray).  The widths are not multiples of 4 (63, 95, 351, 607 columns in front of a segment): a quad may straddle two.
+struct SegRows {
+    struct Seg { const float* ptr; long long ld; int width, per_ray; };
+    Seg seg[4];
+    int nseg, rows, K, n;
+    struct Ctx { int m, ray; };
+    __device__ Ctx prep(int m) const { return m < rows ? Ctx{m, m / n} : Ctx{-1, 0}; }
+    __device__ float at(const Ctx& c, int k) const {   // c.m >= 0, 0 <= k < K
+        float v = 0.0f;
+        int lo = k;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (s < nseg && lo >= 0 && lo < seg[s].width) v = seg[s].ptr[(long long)(seg[s].per_ray ? c.ray : c.m) * seg[s].ld + lo];
+            lo -= s < nseg ? seg[s].width : 0;
+        }
+        return v;
+    }
+    __device__ void load4(const Ctx& c, int k0, int kq, float (&v)[4]) const {
+        const int k = k0 + kq;
+        v[0] = v[1] = v[2] = v[3] = 0.0f;
+        if (c.m < 0 || k >= K) return;
+        int lo = k;                                    // the quad's first column, counted from the segment's first
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (s < nseg && lo + 3 >= 0 && lo < seg[s].width) {
+                const float* row = seg[s].ptr + (long long)(seg[s].per_ray ? c.ray : c.m) * seg[s].ld;
+                if (lo >= 0 && lo + 3 < seg[s].width && ((reinterpret_cast<size_t>(row + lo) & 15) == 0)) {
+                    const float4 t = *reinterpret_cast<const float4*>(row + lo);
+                    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (lo + j >= 0 && lo + j < seg[s].width) v[j] = row[lo + j];
+                }
+            }
+            lo -= s < nseg ? seg[s].width : 0;
         }
     }
 };
@@ -170,7 +214,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(AL al, DenseRows bl, GemmOut 
     const int g = lane >> 4, n16 = lane & 15;
     const int wm = wave >> 1, wn = wave & 1;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    al.p += (long long)blockIdx.z * al.batch_stride;
+    if constexpr (!std::is_same<AL, SegRows>::value) al.p += (long long)blockIdx.z * al.batch_stride;   // (SegRows: one batch)
     bl.p += (long long)blockIdx.z * bl.batch_stride;
     if constexpr (B_PRE) bl.h16 += (long long)blockIdx.z * bl.batch_stride, bl.l16 += (long long)blockIdx.z * bl.batch_stride;
     if constexpr (A_PRE) al.h16 += (long long)blockIdx.z * al.batch_stride, al.l16 += (long long)blockIdx.z * al.batch_stride;
@@ -679,6 +723,62 @@ __global__ void __launch_bounds__(256) transpose_ld_half_kernel(const float* __r
             hi[o] = h, lo[o] = (half_t)(v - (float)h);
         }
 }
+// transpose_ld_half_kernel for the style trainer's segmented layer input: hi / lo [K, ld_out] fp16 straight from the segments
+__global__ void __launch_bounds__(256) transpose_seg_half_kernel(SegRows al, half_t* __restrict__ hi, half_t* __restrict__ lo,
+                                                                 long long ld_out) {
+    __shared__ float tile[32][33];
+    const int by = blockIdx.y * 32, bx = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int j = ty; j < 32; j += 8)
+        if (by + j < al.rows && bx + tx < al.K) tile[j][tx] = al.at(al.prep(by + j), bx + tx);
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8)
+        if (bx + j < al.K && by + tx < al.rows) {
+            const float v = tile[tx][j];
+            const half_t h = (half_t)v;
+            const long long o = (long long)(bx + j) * ld_out + by + tx;
+            hi[o] = h, lo[o] = (half_t)(v - (float)h);
+        }
+}
+// columns [0, cols) of in [rows, ld_in] -> out [cols, rows] fp32 and, with `hi`, its fp16 hi / lo halves (split_kernel's):
+// a row sub-block of a transposed weight as the B operand of the dx GEMM
+__global__ void __launch_bounds__(256) transpose_sub_kernel(const float* __restrict__ in, long long ld_in, int rows, int cols,
+                                                            float* __restrict__ out, half_t* __restrict__ hi,
+                                                            half_t* __restrict__ lo) {
+    __shared__ float tile[32][33];
+    const int by = blockIdx.y * 32, bx = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int j = ty; j < 32; j += 8)
+        if (by + j < rows && bx + tx < cols) tile[j][tx] = in[(long long)(by + j) * ld_in + bx + tx];
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8)
+        if (bx + j < cols && by + tx < rows) {
+            const float v = tile[tx][j];
+            const long long o = (long long)(bx + j) * rows + by + tx;
+            out[o] = v;
+            if (hi) {
+                const half_t h = (half_t)v;
+                hi[o] = h, lo[o] = (half_t)(v - (float)h);
+            }
+        }
+}
+// out[r, c] = sum over the n samples of ray r of scale * gated dy[r*n + i, c]: what the ray's latent row sees of a layer's
+// gradient (the latent columns of the weight multiply this sum once, not every sample)
+__global__ void __launch_bounds__(256) ray_sum_kernel(const float* __restrict__ dy, const float* __restrict__ gate, long long R,
+                                                      int n, int cols, const float* __restrict__ scale,
+                                                      float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= R * cols) return;
+    const long long r = i / cols;
+    const int c = (int)(i - r * cols);
+    const float sc = *scale;
+    float s = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const long long o = (r * n + j) * cols + c;
+        s += (gate && !(gate[o] > 0.0f)) ? 0.0f : dy[o] * sc;
+    }
+    out[i] = s;
+}
 // Gradients arrive many orders of magnitude below 1 (a mean over the batch sits in front of them), below the range in which
 // an fp16 hi/lo split is exact.  They are rescaled by a power of two -- largest magnitude to ~2^10 -- on their way into the
 // GEMM operands and the products scaled back; the factor never leaves the device.
@@ -926,7 +1026,8 @@ static int launch_gemm(const tgtc_style2d* h, AL al, DenseRows bl, GemmOut out, 
                 return TGTC_OK;
             }
         }
-        if constexpr (std::is_same<AL, DenseRows>::value || std::is_same<AL, ConvNHWC>::value) {
+        // (SegRows: the style trainer's layers take the tile and the B path of the same layer on DenseRows)
+        if constexpr (std::is_same<AL, DenseRows>::value || std::is_same<AL, ConvNHWC>::value || std::is_same<AL, SegRows>::value) {
             if (pre) {
                 if (mid < 400) go(ic<1>{}, std::true_type{});
                 else go(ic<2>{}, std::true_type{});
@@ -1543,6 +1644,294 @@ extern "C" int tgtc_s2d_linear_backward(const float* x, const float* dy, const f
         TGTC_HIP_CHECK(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), st));
         rowsum_kernel<<<dim3(N, nsplit), 256, 0, st>>>(dth, dtl, M, mpad, mc, db, sc + 2);
         TGTC_LAUNCH_CHECK();
+    }
+    return TGTC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ style trainer
+// include/tgtc_train.h: the 13 linears of the two style MLPs as a chain of the per-layer GEMMs above.  Forward: one GEMM per
+// layer on a SegRows A operand.  Backward, per layer from the head down: the scales of tgtc_s2d_linear_backward, dx for the
+// hidden columns only (a row sub-block of W^T), the ray-summed gradient times the latent columns, dW from the transposed
+// gradient and the transposed segments, db.
+namespace tgtc {
+
+enum ChainSrc { SRC_X, SRC_REMAP, SRC_LAT, SRC_H };   // SRC_H: the previous layer's output plane
+struct ChainLayer {
+    int K, N, relu, nseg, src[4];
+    int h_col, lat_col;   // first column of the hidden / latent segment in the weight (h_col -1: no hidden input)
+};
+constexpr int kChainLayers = 13, kChainPlanes = 12, kChainConcat = 5, kChainWRows = 288;   // W^T rows kept: 256 hidden + 32 latent
+#define TGTC_CHAIN_HL {288, 256, 1, 2, {SRC_H, SRC_LAT, 0, 0}, 0, 256}
+#define TGTC_CHAIN_HLX {351, 256, 1, 3, {SRC_H, SRC_LAT, SRC_X, 0}, 0, 256}
+static const ChainLayer kChain[kChainLayers] = {
+    {95, 256, 1, 2, {SRC_X, SRC_LAT, 0, 0}, -1, 63}, TGTC_CHAIN_HL, TGTC_CHAIN_HL, TGTC_CHAIN_HL, TGTC_CHAIN_HLX,        // concat
+    {607, 256, 1, 4, {SRC_REMAP, SRC_H, SRC_X, SRC_LAT}, 256, 575}, TGTC_CHAIN_HL, TGTC_CHAIN_HL, TGTC_CHAIN_HL,         // style
+    TGTC_CHAIN_HLX, TGTC_CHAIN_HL, TGTC_CHAIN_HL, {288, 3, 0, 2, {SRC_H, SRC_LAT, 0, 0}, 0, 256}};
+#undef TGTC_CHAIN_HL
+#undef TGTC_CHAIN_HLX
+
+struct ChainCall {   // what a backward needs to know of its forward
+    const float *x, *remap, *lat_c, *lat_s;
+    int64_t R;
+    int n, precision;
+};
+
+struct ChainLayout {   // byte offsets into the workspace
+    size_t plane[kChainPlanes], rgb;                         // kept from forward to backward
+    size_t g[2], dpre, sc, dyT, xT, part, WT, w16, dys, row_inv, dsum, dsums, ray_inv, total;
+};
+static ChainLayout chain_layout(int64_t R, int n) {
+    ChainLayout L{};
+    const size_t M = (size_t)R * n;
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        const size_t o = off;
+        off += (floats * sizeof(float) + 255) & ~(size_t)255;
+        return o;
+    };
+    for (int i = 0; i < kChainPlanes; ++i) L.plane[i] = take(M * 256);
+    L.rgb = take(M * 3);
+    size_t dyT = 0, xT = 0, part = 0;
+    for (const ChainLayer& l : kChain) {
+        int nsplit;
+        int64_t mc;
+        backward_split((int64_t)M, l.K, l.N, nsplit, mc);
+        const size_t mpad = (size_t)nsplit * mc;
+        dyT = std::max(dyT, l.N * mpad), xT = std::max(xT, l.K * mpad), part = std::max(part, (size_t)nsplit * l.N * l.K);
+    }
+    L.g[0] = take(M * 256), L.g[1] = take(M * 256), L.dpre = take(M * 3), L.sc = take(64);
+    L.dyT = take(dyT), L.xT = take(xT), L.part = take(part);
+    L.WT = take((size_t)kChainWRows * 256), L.w16 = take((size_t)kChainWRows * 256);   // w16: hi, then lo, halves
+    L.dys = take(M * 256), L.row_inv = take(M);
+    L.dsum = take((size_t)R * 256), L.dsums = take((size_t)R * 256), L.ray_inv = take((size_t)R);
+    L.total = off;
+    return L;
+}
+
+static SegRows chain_rows(int g, const ChainCall& c, char* ws, const ChainLayout& L) {
+    const ChainLayer& l = kChain[g];
+    SegRows a{};
+    a.nseg = l.nseg, a.rows = (int)(c.R * c.n), a.K = l.K, a.n = c.n;
+    for (int s = 0; s < l.nseg; ++s) {
+        switch (l.src[s]) {
+            case SRC_X: a.seg[s] = {c.x, 63, 63, 0}; break;
+            case SRC_REMAP: a.seg[s] = {c.remap, 256, 256, 0}; break;
+            case SRC_LAT: a.seg[s] = {g < kChainConcat ? c.lat_c : c.lat_s, 32, 32, 1}; break;
+            default: a.seg[s] = {reinterpret_cast<const float*>(ws + L.plane[g - 1]), 256, 256, 0}; break;
+        }
+    }
+    return a;
+}
+
+// M = R * n samples at most 65 535 x 32: the transposes of the weight-gradient operands put 32 samples on each grid.y block
+constexpr int64_t kChainMaxSamples = 65535LL * 32;
+static bool chain_shape_ok(int64_t R, int n) { return R >= 0 && n > 0 && R <= kChainMaxSamples / n; }
+
+// one layer's backward; dy [M,N] is the gradient of the layer's output, `gate` that output (ReLU layers) or null
+static int chain_layer_backward(const tgtc_style2d& h, int g, const ChainCall& c, char* ws, const ChainLayout& L, const float* W,
+                                const float* dy, const float* gate, float* dx, float* dW, float* db, float* d_lat,
+                                hipStream_t st) {
+    const ChainLayer& l = kChain[g];
+    const int K = l.K, N = l.N;
+    const int64_t M = c.R * c.n;
+    auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+    int nsplit;
+    int64_t mc;
+    backward_split(M, K, N, nsplit, mc);
+    const long long mpad = (long long)nsplit * mc, mn = (long long)M * N;
+    float *sc = f(L.sc), *WT = f(L.WT), *dys = f(L.dys), *row_inv = f(L.row_inv), *part = f(L.part);
+    TGTC_HIP_CHECK(hipMemsetAsync(sc, 0, 16, st));
+    absmax_kernel<<<(unsigned)std::min<long long>(1024, (mn + 255) / 256), 256, 0, st>>>(dy, mn, reinterpret_cast<unsigned*>(sc), nullptr);
+    TGTC_LAUNCH_CHECK();
+    grad_scale_kernel<<<1, 1, 0, st>>>(sc);
+    TGTC_LAUNCH_CHECK();
+    // rows of W^T: the hidden columns in rows 0..255, the latent columns in rows 256..287, as fp32 and as pre-split halves
+    const bool pre = N % 4 == 0;
+    half_t* wh = reinterpret_cast<half_t*>(f(L.w16));
+    half_t* wl = wh + (size_t)kChainWRows * 256;
+    auto w_rows = [&](int col0, int cols, int row0) {
+        const dim3 grid((cols + 31) / 32, (N + 31) / 32);
+        const size_t o = (size_t)row0 * N;
+        transpose_sub_kernel<<<grid, 256, 0, st>>>(W + col0, K, N, cols, WT + o, pre ? wh + o : nullptr, pre ? wl + o : nullptr);
+    };
+    if (dx && d_lat && l.lat_col == l.h_col + 256) {
+        w_rows(l.h_col, 288, 0);
+    } else {
+        if (dx) w_rows(l.h_col, 256, 0);
+        if (d_lat) w_rows(l.lat_col, 32, 256);
+    }
+    TGTC_LAUNCH_CHECK();
+    if (dx) {   // dx[M,256] = (s_m * gated dy)[M,N] . W[:, hidden columns], row m scaled back by 1/s_m
+        half_t* dyh = reinterpret_cast<half_t*>(dys);
+        half_t* dyl = dyh + (size_t)mn;
+        row_scale_kernel<<<(unsigned)((M + 3) / 4), 256, 0, st>>>(dy, M, N, row_inv);
+        TGTC_LAUNCH_CHECK();
+        if (pre) scale_split_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, N, row_inv, gate, dyh, dyl);
+        else scale_copy_kernel<<<(unsigned)((mn + 255) / 256), 256, 0, st>>>(dy, mn, N, row_inv, dys, gate);
+        TGTC_LAUNCH_CHECK();
+        DenseRows al{dys, N, 0, (int)M, N}, bl{WT, N, 0, 256, N};
+        if (pre) al.h16 = dyh, al.l16 = dyl, bl.h16 = wh, bl.l16 = wl;
+        GemmOut out{dx, 256, 1, 0, nullptr, nullptr, 1.0f, 0};
+        out.row_alpha = row_inv;
+        TGTC_TRY((launch_gemm<DenseRows, false>(&h, al, bl, out, (int)M, 256, N, 1, st)));
+    }
+    if (d_lat) {   // d_lat[R,32] += (sum over the ray's samples of s * gated dy)[R,N] . W[:, latent columns] / s
+        const long long rn = (long long)c.R * N;
+        float *dsum = f(L.dsum), *dsums = f(L.dsums), *ray_inv = f(L.ray_inv);
+        half_t* sh = reinterpret_cast<half_t*>(dsums);
+        half_t* sl = sh + (size_t)rn;
+        ray_sum_kernel<<<(unsigned)((rn + 255) / 256), 256, 0, st>>>(dy, gate, c.R, c.n, N, sc + 1, dsum);
+        TGTC_LAUNCH_CHECK();
+        row_scale_kernel<<<(unsigned)((c.R + 3) / 4), 256, 0, st>>>(dsum, c.R, N, ray_inv);
+        TGTC_LAUNCH_CHECK();
+        if (pre) scale_split_kernel<<<(unsigned)((rn + 255) / 256), 256, 0, st>>>(dsum, rn, N, ray_inv, nullptr, sh, sl);
+        else scale_copy_kernel<<<(unsigned)((rn + 255) / 256), 256, 0, st>>>(dsum, rn, N, ray_inv, dsums, nullptr);
+        TGTC_LAUNCH_CHECK();
+        const size_t o = (size_t)256 * N;
+        DenseRows al{dsums, N, 0, (int)c.R, N}, bl{WT + o, N, 0, 32, N};
+        if (pre) al.h16 = sh, al.l16 = sl, bl.h16 = wh + o, bl.l16 = wl + o;
+        GemmOut out{d_lat, 32, 1, 0, nullptr, d_lat, 1.0f, 0};
+        out.row_alpha = ray_inv, out.alpha_dev = sc + 2;
+        TGTC_TRY((launch_gemm<DenseRows, false>(&h, al, bl, out, (int)c.R, 32, N, 1, st)));
+    }
+    // dW, db: tgtc_s2d_linear_backward's, with x^T written from the segments
+    half_t* dth = reinterpret_cast<half_t*>(f(L.dyT));
+    half_t* dtl = dth + (size_t)N * mpad;
+    half_t* xh = reinterpret_cast<half_t*>(f(L.xT));
+    half_t* xl = xh + (size_t)K * mpad;
+    if (mpad > M) {   // only the pad columns: the transposes write the rest
+        const size_t pitch = (size_t)mpad * sizeof(half_t), wide = (size_t)(mpad - M) * sizeof(half_t);
+        TGTC_HIP_CHECK(hipMemset2DAsync(dth + M, pitch, 0, wide, N, st));
+        TGTC_HIP_CHECK(hipMemset2DAsync(dtl + M, pitch, 0, wide, N, st));
+        TGTC_HIP_CHECK(hipMemset2DAsync(xh + M, pitch, 0, wide, K, st));
+        TGTC_HIP_CHECK(hipMemset2DAsync(xl + M, pitch, 0, wide, K, st));
+    }
+    transpose_ld_half_kernel<<<dim3((N + 31) / 32, (unsigned)((M + 31) / 32)), 256, 0, st>>>(dy, M, N, dth, dtl, mpad, sc + 1, gate);
+    TGTC_LAUNCH_CHECK();
+    transpose_seg_half_kernel<<<dim3((K + 31) / 32, (unsigned)((M + 31) / 32)), 256, 0, st>>>(chain_rows(g, c, ws, L), xh, xl, mpad);
+    TGTC_LAUNCH_CHECK();
+    DenseRows al{f(L.dyT), mpad, mc, N, (int)mc}, bl{f(L.xT), mpad, mc, K, (int)mc};
+    al.h16 = dth, al.l16 = dtl;
+    bl.h16 = xh, bl.l16 = xl;
+    GemmOut out{nsplit > 1 ? part : dW, K, 1, (long long)N * K, nullptr, nullptr, 1.0f, 0};
+    out.alpha_dev = sc + 2;
+    TGTC_TRY((launch_gemm<DenseRows, false>(&h, al, bl, out, N, K, (int)mc, nsplit, st)));
+    if (nsplit > 1) {
+        const long long nk = (long long)N * K;
+        sum_partials_kernel<<<(unsigned)((nk + 255) / 256), 256, 0, st>>>(part, nsplit, nk, dW);
+        TGTC_LAUNCH_CHECK();
+    }
+    TGTC_HIP_CHECK(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), st));
+    rowsum_kernel<<<dim3(N, nsplit), 256, 0, st>>>(dth, dtl, M, mpad, mc, db, sc + 2);
+    TGTC_LAUNCH_CHECK();
+    return TGTC_OK;
+}
+
+}  // namespace tgtc
+
+struct tgtc_style_trainer {
+    std::mutex mu;
+    std::map<const void*, ChainCall> calls;   // by workspace: the forward it holds
+};
+
+extern "C" int tgtc_style_trainer_create(tgtc_style_trainer** out) {
+    TGTC_REQUIRE(out, "style_trainer_create: null argument");
+    *out = new tgtc_style_trainer();
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_style_trainer_destroy(tgtc_style_trainer* tr) {
+    delete tr;
+    return TGTC_OK;
+}
+
+extern "C" size_t tgtc_style_trainer_workspace_bytes(int64_t R, int n) {
+    return chain_shape_ok(R, n) && R > 0 ? chain_layout(R, n).total : 0;
+}
+
+extern "C" int tgtc_style_trainer_forward(tgtc_style_trainer* tr, const float* const* params, const float* x,
+                                          const float* base_remap, const float* lat_c, const float* lat_s, int64_t R, int n,
+                                          int precision, void* workspace, size_t workspace_bytes, float* rgb, void* stream) {
+    TGTC_REQUIRE(tr, "style_trainer_forward: null trainer");
+    TGTC_REQUIRE(chain_shape_ok(R, n), "style_trainer_forward: bad shape (R >= 0, n > 0, R * n <= 2 097 120)");
+    TGTC_REQUIRE(precision == TGTC_PREC_FP16 || precision == TGTC_PREC_FP16X3, "style_trainer_forward: precision %d (fp16x3 or fp16)", precision);
+    if (R == 0) return TGTC_OK;
+    TGTC_REQUIRE(params && x && base_remap && lat_c && lat_s && rgb && workspace, "style_trainer_forward: null pointer");
+    for (int i = 0; i < 2 * kChainLayers; ++i) TGTC_REQUIRE(params[i], "style_trainer_forward: params[%d] is null", i);
+    const ChainLayout L = chain_layout(R, n);
+    TGTC_REQUIRE(workspace_bytes >= L.total, "style_trainer_forward: workspace of %zu bytes, needs %zu", workspace_bytes, L.total);
+    hipStream_t st = as_stream(stream);
+    tgtc_style2d h;
+    h.precision = precision;
+    char* ws = static_cast<char*>(workspace);
+    const ChainCall c{x, base_remap, lat_c, lat_s, R, n, precision};
+    const int M = (int)(R * n);
+    half_t* wh = reinterpret_cast<half_t*>(ws + L.w16);
+    for (int g = 0; g < kChainLayers; ++g) {
+        const ChainLayer& l = kChain[g];
+        DenseRows bl{params[2 * g], l.K, 0, l.N, l.K};
+        if (l.K % 4 == 0) {   // the weight as pre-split halves, as tgtc_s2d_split hands them to tgtc_s2d_linear_pre
+            const long long nk = (long long)l.N * l.K;
+            split_kernel<<<(unsigned)((nk + 255) / 256), 256, 0, st>>>(params[2 * g], nk, wh, wh + nk);
+            TGTC_LAUNCH_CHECK();
+            bl.h16 = wh, bl.l16 = wh + nk;
+        }
+        float* y = reinterpret_cast<float*>(ws + (g < kChainPlanes ? L.plane[g] : L.dpre));
+        GemmOut out{y, l.N, 1, 0, params[2 * g + 1], nullptr, 1.0f, l.relu};
+        TGTC_TRY((launch_gemm<SegRows, false>(&h, chain_rows(g, c, ws, L), bl, out, M, l.N, l.K, 1, st)));
+    }
+    const long long m3 = (long long)M * 3;
+    act_kernel<<<(unsigned)((m3 + 255) / 256), 256, 0, st>>>(reinterpret_cast<const float*>(ws + L.dpre), nullptr, m3, 2, rgb);
+    TGTC_LAUNCH_CHECK();
+    TGTC_HIP_CHECK(hipMemcpyAsync(ws + L.rgb, rgb, (size_t)m3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    std::lock_guard<std::mutex> lock(tr->mu);
+    tr->calls[workspace] = c;
+    return TGTC_OK;
+}
+
+extern "C" int tgtc_style_trainer_backward(tgtc_style_trainer* tr, const float* const* params, const float* d_rgb, int64_t R,
+                                           int n, void* workspace, size_t workspace_bytes, float* const* grads, float* d_lat_c,
+                                           float* d_lat_s, void* stream) {
+    TGTC_REQUIRE(tr, "style_trainer_backward: null trainer");
+    TGTC_REQUIRE(chain_shape_ok(R, n), "style_trainer_backward: bad shape (R >= 0, n > 0, R * n <= 2 097 120)");
+    TGTC_REQUIRE(grads, "style_trainer_backward: null pointer");
+    for (int i = 0; i < 2 * kChainLayers; ++i) TGTC_REQUIRE(grads[i], "style_trainer_backward: grads[%d] is null", i);
+    hipStream_t st = as_stream(stream);
+    if (R == 0) {   // an empty batch: every gradient is zero
+        for (int g = 0; g < kChainLayers; ++g) {
+            TGTC_HIP_CHECK(hipMemsetAsync(grads[2 * g], 0, (size_t)kChain[g].N * kChain[g].K * sizeof(float), st));
+            TGTC_HIP_CHECK(hipMemsetAsync(grads[2 * g + 1], 0, (size_t)kChain[g].N * sizeof(float), st));
+        }
+        return TGTC_OK;
+    }
+    TGTC_REQUIRE(params && d_rgb && workspace, "style_trainer_backward: null pointer");
+    for (int i = 0; i < 2 * kChainLayers; ++i) TGTC_REQUIRE(params[i], "style_trainer_backward: params[%d] is null", i);
+    const ChainLayout L = chain_layout(R, n);
+    TGTC_REQUIRE(workspace_bytes >= L.total, "style_trainer_backward: workspace of %zu bytes, needs %zu", workspace_bytes, L.total);
+    ChainCall c;
+    {
+        std::lock_guard<std::mutex> lock(tr->mu);
+        const auto it = tr->calls.find(workspace);
+        TGTC_REQUIRE(it != tr->calls.end() && it->second.R == R && it->second.n == n,
+                     "style_trainer_backward: this workspace holds no forward of %lld rays x %d samples", (long long)R, n);
+        c = it->second;
+        tr->calls.erase(it);
+    }
+    tgtc_style2d h;
+    h.precision = c.precision;
+    char* ws = static_cast<char*>(workspace);
+    auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+    const long long m3 = (long long)R * n * 3;
+    act_kernel<<<(unsigned)((m3 + 255) / 256), 256, 0, st>>>(d_rgb, f(L.rgb), m3, 1, f(L.dpre));   // through the sigmoid
+    TGTC_LAUNCH_CHECK();
+    if (d_lat_c) TGTC_HIP_CHECK(hipMemsetAsync(d_lat_c, 0, (size_t)R * 32 * sizeof(float), st));
+    if (d_lat_s) TGTC_HIP_CHECK(hipMemsetAsync(d_lat_s, 0, (size_t)R * 32 * sizeof(float), st));
+    const float* dy = f(L.dpre);
+    for (int g = kChainLayers - 1, flip = 0; g >= 0; --g) {
+        float* dx = kChain[g].h_col >= 0 ? f(L.g[flip]) : nullptr;
+        TGTC_TRY(chain_layer_backward(h, g, c, ws, L, params[2 * g], dy, g < kChainPlanes ? f(L.plane[g]) : nullptr, dx,
+                                      grads[2 * g], grads[2 * g + 1], g < kChainConcat ? d_lat_c : d_lat_s, st));
+        dy = dx, flip ^= 1;
     }
     return TGTC_OK;
 }

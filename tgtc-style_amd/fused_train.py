@@ -27,8 +27,16 @@ SIGNATURES = {
     "tgtc_trainer_set_sparse": [c_void_p, c_int],
     "tgtc_trainer_workspace_bytes_sparse": [c_int64],
     "tgtc_trainer_live_counts": [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)],
+    # the style trainer of the same header (style_chain.py)
+    "tgtc_style_trainer_create": [ctypes.POINTER(c_void_p)],
+    "tgtc_style_trainer_destroy": [c_void_p],
+    "tgtc_style_trainer_workspace_bytes": [c_int64, c_int],
+    "tgtc_style_trainer_forward": [c_void_p, _PTRS, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t,
+                                   c_void_p, c_void_p],
+    "tgtc_style_trainer_backward": [c_void_p, _PTRS, c_void_p, c_int64, c_int, c_void_p, c_size_t, _PTRS, c_void_p, c_void_p, c_void_p],
 }
-hip.register(SIGNATURES, {"tgtc_trainer_workspace_bytes": c_size_t, "tgtc_trainer_workspace_bytes_sparse": c_size_t})
+hip.register(SIGNATURES, {"tgtc_trainer_workspace_bytes": c_size_t, "tgtc_trainer_workspace_bytes_sparse": c_size_t,
+                          "tgtc_style_trainer_workspace_bytes": c_size_t})
 TRAIN_DENSE, TRAIN_SPARSE = 0, 1     # include/tgtc_train.h
 
 

@@ -161,6 +161,10 @@ def style_train(args, model, model_fine, concat_model, style_model, latents, dat
         for group in style_optimizer.param_groups:
             group['lr'] = args.lrate
     latent_optimizer = torch.optim.Adam([latents.latents], lr=args.latent_lrate)          # models.py:541-542
+    chain = None
+    if getattr(args, "style_chain", False):          # --style_chain: only ever the caller's choice
+        from . import style_chain
+        chain = style_chain.StyleTrainer()
     seed = getattr(args, "train_seed", 0)
     seeded = seed is not None and seed >= 0
     B = args.batch_size_style
@@ -185,7 +189,7 @@ def style_train(args, model, model_fine, concat_model, style_model, latents, dat
             args.N_samples, n_fine, data.near, data.far, coherence, sigma_noise_std=args.sigma_noise_std,
             rgb_loss_lambda=args.rgb_loss_lambda, logp_loss_lambda=logp_weight(args, global_step),
             loss_coh_lambda=args.loss_coh_lambda, coh_in_loss=with_coh, data_type=args.dataset_type, generator=gen,
-            check_ids=False, as_float=False)
+            check_ids=False, as_float=False, chain=chain)
         acc += torch.stack([r['loss'], r['total'], r['loss_rgb']])
         window += 1
         if global_step % args.i_print == 0 or global_step == first:

@@ -467,6 +467,16 @@ def main(argv=None):
                              "runs no backward)" % " / --".join(renders))
         if not args.origin_train:
             raise SystemExit("train_tgtcs: --train_sparse needs --origin_train (it is the backward of that stage)")
+    if args.style_chain:
+        renders = [f for f in ("render_valid", "render_train", "render_valid_style", "render_train_style") if getattr(args, f)]
+        if args.origin_train:
+            raise SystemExit("train_tgtcs: --style_chain goes with --style_train; it does not go with --origin_train (the "
+                             "style MLPs are not trained there)")
+        if renders:
+            raise SystemExit("train_tgtcs: --style_chain goes with --style_train; it does not go with --%s (a render "
+                             "runs no backward)" % " / --".join(renders))
+        if not args.style_train:
+            raise SystemExit("train_tgtcs: --style_chain needs --style_train (it is the style MLPs' step of that stage)")
     if args.origin_train and args.style_train:
         raise SystemExit("train_tgtcs: --origin_train and --style_train are two stages: one call each, in that order")
     for stage in ("origin_train", "style_train"):

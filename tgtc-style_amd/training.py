@@ -9,8 +9,11 @@ checkpoint cadence, logging -- is train_loop.origin_train (`train_tgtcs --origin
 
 `style_train_step` is the body of the reference's `Style_train` (train_tgtcs.py:352-482) batch by batch, as the reference
 runs it; `style_train_iteration` is the same iteration for the loop train_loop.style_train (`train_tgtcs --style_train`):
-both batches in one pass over the operators and the reference's two optimisers from one backward.  Both stay on the
-per-layer path for the two style MLPs (autograd_ops.py).  The VGG content / style losses of the reference's later stages
+both batches in one pass over the operators and the reference's two optimisers from one backward.  Both run the two style
+MLPs on the per-layer path (autograd_ops.py) unless the caller hands them a `chain` (style_chain.StyleTrainer): the two
+module forwards of a pass are then one call of the library's style trainer (include/tgtc_train.h) -- the same per-layer
+arithmetic, chained inside the library.  `chain=None`, the default, is the per-layer path; nothing selects the chain for the
+caller.  The VGG content / style losses of the reference's later stages
 and the training of the 2-D module stay outside this build."""
 import torch
 
@@ -107,7 +110,7 @@ class CoherenceState:
 def style_train_step(model, model_fine, concat_model, style_model, latents, optimizer, rays_o, rays_d, rgb_gt, style_ids,
                      frame_ids, N_samples, N_samples_fine, near, far, sigma_noise_std=1.0, rgb_loss_lambda=1.0,
                      logp_loss_lambda=0.0, data_type='llff', jitter=None, coherence=None, coh_batch=None,
-                     loss_coh_lambda=0.0, as_float=True):
+                     loss_coh_lambda=0.0, as_float=True, chain=None):
     """One `Style_train` iteration (train_tgtcs.py:352-482): the shuffled batch's rendering, pixel and -log p terms and,
     with `coherence` (a CoherenceState) and `coh_batch` (dict rays_o, rays_d, rgb_origin, style_id, frame_id [, jitter]: the
     frame-ordered batch of `loss_coh_get_batch`, :366-370), the cosine-coherence term between consecutive frame-ordered
@@ -124,6 +127,8 @@ def style_train_step(model, model_fine, concat_model, style_model, latents, opti
         def one_pass(nerf, pts, n):
             with torch.no_grad():
                 ret = nerf(pts=pts, dirs=rd.unsqueeze(1).expand([R, n, 3]))
+            if chain is not None:
+                return chain.apply(concat_model, style_model, ret['pts'], ret['base_remap'], z, zbar.expand(R, L), n), ret['sigma']
             cf = concat_model(x=ret['pts'], latent=z.unsqueeze(1).expand([R, n, L]))['concat_features']
             both = torch.cat((ret['base_remap'], cf), dim=-1)
             rgb = style_model(x=ret['pts'], concated=both, latent=zbar.unsqueeze(2).expand([R, n, L]))['rgb']
@@ -166,7 +171,7 @@ def style_train_step(model, model_fine, concat_model, style_model, latents, opti
 def style_train_iteration(model, model_fine, concat_model, style_model, latents, style_optimizer, latent_optimizer, batch, R,
                           N_samples, N_samples_fine, near, far, coherence, sigma_noise_std=1.0, rgb_loss_lambda=1.0,
                           logp_loss_lambda=0.0, loss_coh_lambda=0.0, coh_in_loss=True, data_type='llff', jitter=None,
-                          generator=None, check_ids=True, as_float=False):
+                          generator=None, check_ids=True, as_float=False, chain=None):
     """The same `Style_train` iteration as `style_train_step` with its coherence batch, for the loop
     (train_loop.style_train): BOTH batches in ONE pass, and the reference's two optimisers from ONE backward.
 
@@ -208,6 +213,8 @@ def style_train_iteration(model, model_fine, concat_model, style_model, latents,
     def one_pass(nerf, pts, n):
         with torch.no_grad():
             ret = nerf(pts=pts, dirs=rd.unsqueeze(1).expand([T, n, 3]))
+        if chain is not None:
+            return chain.apply(concat_model, style_model, ret['pts'], ret['base_remap'], z, zbar.expand(T, L), n), ret['sigma']
         cf = concat_model(x=ret['pts'], latent=z.unsqueeze(1).expand([T, n, L]))['concat_features']
         both = torch.cat((ret['base_remap'], cf), dim=-1)
         rgb = style_model(x=ret['pts'], concated=both, latent=zbar.unsqueeze(2).expand([T, n, L]))['rgb']

@@ -14,7 +14,17 @@ batch_size_style 256 (fern's) and 1 024.
 A and B alternate in one process, ROUNDS times, and the spread of each is reported.  The batch call is timed on its own,
 issued back to back (host enqueue included), next to tgtc_train_batch on the same rows.
 
-Prints and writes profiles/style_train_loop_timing.json (or the path given).  Needs a GPU: there is no fallback."""
+Prints and writes profiles/style_train_loop_timing.json (or the path given).  Needs a GPU: there is no fallback.
+
+    time_style_train_loop.py chain [path]
+
+times a third variant against B instead, ROUNDS_CHAIN rounds each, alternated in one process:
+
+    C = B with `--style_chain`: the two style MLPs of a pass through the library's style trainer
+        (tgtc_style_trainer_forward / _backward, style_chain.StyleTrainer) instead of the per-layer path
+
+and writes profiles/style_chain_timing.json (or the path given): milliseconds per step of both with min .. max over the
+rounds, and whether the two ranges overlap."""
 import json
 import os
 import sys
@@ -31,6 +41,7 @@ from tgtc_style_amd import config as cfg, models, synth, train_data, train_loop,
 HW = 100
 BATCHES = (256, 1024)
 ROUNDS = 3
+ROUNDS_CHAIN = 5
 STEPS_A, WARM_A = 40, 8
 I_PRINT, LOOP_STEPS = 25, 75            # lines at 0, 25, 50, 75: the first window is warm-up
 FERN = os.path.join(ROOT, "configs", "fern.txt")
@@ -89,9 +100,9 @@ def two_pass_step(args, data, batch):
         coherence=coherence, coh_batch=coh_batch, loss_coh_lambda=args.loss_coh_lambda, as_float=False), STEPS_A, WARM_A)
 
 
-def loop(data, batch):
+def loop(data, batch, chain=False):
     a = cfg.parse_args(["--config", FERN, "--batch_size_style", str(batch), "--total_step", str(LOOP_STEPS), "--i_print",
-                        str(I_PRINT), "--i_weights", "1000000", "--train_seed", "0"])
+                        str(I_PRINT), "--i_weights", "1000000", "--train_seed", "0"] + (["--style_chain"] if chain else []))
     m, mf, cm, sm, lat = networks(a, data)
     log = []
     with tempfile.TemporaryDirectory() as sv:
@@ -110,11 +121,44 @@ def batch_call(data, batch):
             "tgtc_train_batch_us": origin}
 
 
+def chain_main(data, args, out_path):
+    """B against C, ROUNDS_CHAIN rounds each, alternated; says whether the two ranges of round means overlap."""
+    result = {"device": torch.cuda.get_device_name(0),
+              "scene": "synthetic, %d style(s), %d frames of %d x %d" % (data.style_num, data.frame_num, HW, HW),
+              "rows": data.data_num, "n_coarse": args.N_samples, "n_fine": args.N_samples_fine, "rounds": ROUNDS_CHAIN,
+              "i_print": I_PRINT, "steady_windows_per_round": LOOP_STEPS // I_PRINT - 1,
+              "B": "train_loop.style_train in steady state, the two style MLPs on the per-layer path (autograd_ops.py)",
+              "C": "the same loop with --style_chain: both style MLPs through tgtc_style_trainer_forward / _backward",
+              "per_batch": {}}
+    for batch in BATCHES:
+        b_ms, c_ms, finals = [], [], {}
+        for _ in range(ROUNDS_CHAIN):
+            for ms, chain in ((b_ms, False), (c_ms, True)):
+                windows, finals["C" if chain else "B"] = loop(data, batch, chain)
+                ms.append(sum(windows) / len(windows))
+        b, c = sum(b_ms) / len(b_ms), sum(c_ms) / len(c_ms)
+        apart = max(c_ms) < min(b_ms) or min(c_ms) > max(b_ms)
+        rec = {"B_per_layer_ms_per_step": b_ms, "C_chain_ms_per_step": c_ms, "B_ms_mean": b, "C_ms_mean": c,
+               "B_ms_min_max": [min(b_ms), max(b_ms)], "C_ms_min_max": [min(c_ms), max(c_ms)], "C_over_B": c / b,
+               "difference_exceeds_the_rounds_spread": apart,
+               "mean_loss_of_the_last_window": finals}
+        result["per_batch"][str(batch)] = rec
+        print("batch_size_style %d: B (per-layer) %.3f ms [%.3f .. %.3f]   C (chain) %.3f ms [%.3f .. %.3f]   C / B %.3f   "
+              "the ranges %s" % (batch, b, min(b_ms), max(b_ms), c, min(c_ms), max(c_ms), c / b,
+                                 "do not overlap" if apart else "OVERLAP: no difference beyond the rounds' spread"), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit("time_style_train_loop: no GPU visible; there is nothing to time without one")
     args = cfg.parse_args(["--config", FERN, "--synthetic", "--synthetic_hw", str(HW), "--synthetic_styles", "1"])
     data = train_data.StyleTrainRays.from_synthetic(args, torch.device("cuda", 0))
+    if len(sys.argv) > 1 and sys.argv[1] == "chain":
+        return chain_main(data, args, sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "style_chain_timing.json"))
     result = {"device": torch.cuda.get_device_name(0),
               "scene": "synthetic, %d style(s), %d frames of %d x %d" % (data.style_num, data.frame_num, HW, HW),
               "rows": data.data_num, "n_coarse": args.N_samples, "n_fine": args.N_samples_fine,
